@@ -1,6 +1,6 @@
 """Device-resident FedAVG-family aggregation throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config ns|c2|c3|c4|c5|c1k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config ns|c2|c3|c4|c5|c1k] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 `--gpus N` with no launcher env starts the N ranks itself (flearn_amd/launch.py: fresh children
@@ -36,6 +36,17 @@ Multi-GPU (element-range column shards + RCCL all-gather, flearn_amd/dist.py):
                    peer); `value` counts every column once ("replicated_cols" in "multi_gpu")
   --emulate-world G  one GPU runs rank 0's share of a G-GPU job (no collective): the per-rank
                    reduce of the multi-GPU runs, measurable on a single-GPU box
+A plain run does what `value` needs and no more: it sets the job up, warms up, times --steps
+steps, and prints the line (`verify`, `cpu_baseline` are then null; so is `roofline` where the step
+is more than one launch).  At N > 1 the plan's calibration and the push phase stay, since they
+choose the timed path, and a push job is still checked before it replaces the RCCL line.
+  --full           adds the self-check of the reassembled model (`verify`; a mismatch exits 3), the
+                   CPU baseline, the roofline's own launches, and at N > 1 the per-rank reduce, the
+                   all-gather probe, the weak job and the loopback
+  --dump-outputs DIR  after the timed steps, writes what the last one computed: DIR/w_glob.npy (the
+                   fp32 global model step() returned) and for c3/c5 DIR/v_t.npy (fp64 optimizer
+                   state, rank 0's columns).  Arrays over 4 Mi elements are sampled at fixed seeded
+                   positions.  Inputs are seeded, so two builds can be compared output for output
 Prints ONE JSON line on rank 0 (stdout); progress goes to stderr.
 """
 from __future__ import annotations
@@ -157,6 +168,7 @@ class Job:
         self.cfg, self.n, self.plan, self.dev = cfg, n, plan, dev
         self.world, self.push, self.push_grid = world, push, push_grid
         self.red = None
+        self.outputs = None  # --dump-outputs: the last timed step's results (snapshot_outputs)
         cols, stride = plan.local_cols, plan.local_stride
         log(f"[rank {plan.rank}] alloc {n} x {cols} fp32 = {n * cols * 4 / 1e9:.2f} GB, stripes {plan.widths}"
             + (f" + replicated tail {plan.rep}" if plan.rep else ""))
@@ -563,6 +575,38 @@ def plan_push(cfg, layout, n, args, world, rank, dev, g_eff, r_big_s):
     return plan, g, info, trials[i]["measured_ms"] * 1e-3
 
 
+DUMP_SEED, DUMP_SAMPLE = 4242, 4 * 1024 * 1024  # --dump-outputs: elements kept of an array larger than that
+
+
+def _dump_sample(t: torch.Tensor) -> torch.Tensor:
+    """The whole of a small array, else DUMP_SAMPLE elements of it at fixed positions (seeded, sorted;
+    they depend on the array's length alone, so two builds dump the same elements)."""
+    t = t.reshape(-1)
+    if t.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_SAMPLE))
+        t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+    return t.detach().cpu().clone()
+
+
+def snapshot_outputs(job, last: torch.Tensor) -> dict:
+    """What the last timed step computed, copied to the host right after the timed region: `w_glob`,
+    the fp32 global model step() returned, and for the fused configs `v_t`, the optimizer state it
+    left (this rank's columns) — at most 4 Mi elements each (16 + 32 MB)."""
+    out = {"w_glob": _dump_sample(last)}
+    st = job.red.state
+    if st is not None:
+        out["v_t"] = _dump_sample(st.v[st.cur][: job.plan.local_cols])
+    return out
+
+
+def write_outputs(outputs: dict, directory: str):
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.numpy()
+        np.save(d / f"{name}.npy", a if a.dtype in (np.float32, np.float64) else a.astype(np.float32))
+
+
 def timed_job(cfg, layout, n, plan, gather, push_grid, args, world, dev, g_eff):
     """Build the job on `plan` with `gather`, warm up, time args.steps steps (barrier + sync on
     both sides, HIP events on the launch stream, max over ranks).  Returns (job, step_s, wall_s,
@@ -578,18 +622,21 @@ def timed_job(cfg, layout, n, plan, gather, push_grid, args, world, dev, g_eff):
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
+    last = None
     for _ in range(args.steps):
-        job.red.step()
+        last = job.red.step()
     ev1.record()
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
+    if args.dump_outputs:  # before anything else steps the job: the fused configs' state moves on
+        job.outputs = snapshot_outputs(job, last)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = max(ev0.elapsed_time(ev1) / 1e3, 0.0)  # s, on the stream the kernels run on
     elapsed, wall = _max_over_ranks((elapsed, wall), world, dev)
     step_s = elapsed / args.steps
-    if g_eff > 1:  # this rank's reduce launches of one step alone (no collective), max over ranks
+    if g_eff > 1 and args.full:  # this rank's reduce launches of one step alone (no collective), max over ranks
         red_s = _max_over_ranks((_event_time(job.reduce_only, max(3, min(args.steps, 20))),), world, dev)[0]
         info["per_rank_reduce_ms"] = round(red_s * 1e3, 4)
         info["exposed_gather_ms"] = round(max(step_s - red_s, 0.0) * 1e3, 4)
@@ -959,13 +1006,16 @@ def job_extras(job, step_s, info, args, cfg, world, dev, g_eff, main_n, backend)
     plan, cols = job.plan, job.plan.local_cols
     if g_eff == 1 and plan.stripes == 1:
         launch_s = step_s  # the step IS one kernel launch
+    elif not args.full:
+        launch_s = None  # a plain run takes no launches beside its timed steps: no roofline
     else:  # the reduce of this rank's whole local width as one launch (no gather)
         launch_s = _max_over_ranks((_event_time(lambda: job.fn(0, cols, job.red.local_out), args.steps),), world, dev)[0]
     if world > 1:
         info["world_size"] = dist.get_world_size()
         info["backend"] = dist.get_backend()
         info["rccl_version"] = rccl_version() if backend == "nccl" else None
-        info["allgather_probe"] = gather_probe(job, world, dev)
+        if args.full:
+            info["allgather_probe"] = gather_probe(job, world, dev)
         cal = info.get("calibration")
         if cal and cal.get("measured_gather"):
             c_cols, g_us = cal["width_cols"][0], cal["gather_us"][0]
@@ -981,16 +1031,18 @@ def build_line(args, cfg, world, g_eff, emu, main_n, job, step_s, wall, info, ch
     value = job_bytes / GIB / step_s
     # fa_reduce_f32 may run a wide window as several launches of consecutive column windows
     # (fa_reduce_windows): the per-launch bytes and time are the step's divided by that count
-    launches = max(1, na.lib().fa_reduce_windows(na.OP_BY_NAME[cfg["op"]], cols))
-    launch_bytes = algorithmic_bytes(main_n, cols, cfg["op"]) // launches
-    launch_s = launch_s / launches
-    achieved = launch_bytes / 1e9 / launch_s
-    traffic, traffic_src = load_traffic(args.config) if g_eff == 1 else (None, None)
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "bytes_per_launch": launch_bytes,
-                "launch_us": round(launch_s * 1e6, 2), "launches_per_step": launches}
-    if traffic_src:
-        roofline["traffic_source"] = traffic_src
+    roofline = None  # (launch_s None: a plain run whose step is more than one launch measured none)
+    if launch_s is not None:
+        launches = max(1, na.lib().fa_reduce_windows(na.OP_BY_NAME[cfg["op"]], cols))
+        launch_bytes = algorithmic_bytes(main_n, cols, cfg["op"]) // launches
+        launch_s = launch_s / launches
+        achieved = launch_bytes / 1e9 / launch_s
+        traffic, traffic_src = load_traffic(args.config) if g_eff == 1 else (None, None)
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "bytes_per_launch": launch_bytes,
+                    "launch_us": round(launch_s * 1e6, 2), "launches_per_step": launches}
+        if traffic_src:
+            roofline["traffic_source"] = traffic_src
     weak_main = args.scaling == "weak" and g_eff > 1
     gather = info.get("gather")
     line = {
@@ -1000,6 +1052,7 @@ def build_line(args, cfg, world, g_eff, emu, main_n, job, step_s, wall, info, ch
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(step_s * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak" if weak_main else "strong",
@@ -1183,7 +1236,18 @@ def main():
                          "this many seconds of the start, budget included (the driver's limit is ~600 s)")
     ap.add_argument("--no-loopback", action="store_true",
                     help="N>1: skip the single-process AVG(devices=[...]) loopback measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the self-check of the reassembled model, the CPU baseline, the "
+                         "roofline's own launches, and at N>1 the per-rank reduce, the all-gather probe, the weak "
+                         "job and the loopback (off by default: a plain run times its steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (w_glob fp32; v_t fp64 for the "
+                         "fused configs; a fixed seeded sample of 4 Mi elements of a larger array)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_weak = args.no_loopback = True
     t_start = time.monotonic()
 
     def time_for(budget: float) -> bool:  # may an optional phase of this budget still start?
@@ -1224,8 +1288,9 @@ def main():
     held = HeldLine(rank, lastwords=world > 1)  # multi-GPU: a crash in a later phase still prints the line
     dog = Watchdog(held, rank) if world > 1 else None
 
-    def self_check(job):
-        if args.no_verify:
+    def self_check(job, gates_adoption=False):
+        # a plain run checks only a push job, which replaces the RCCL line only if verified
+        if args.no_verify or not (args.full or gates_adoption):
             return None
         log(f"[rank {rank}] verifying the reassembled model ...")
         c = verify_job(job, cfg, world, dev, emulated=bool(emu))
@@ -1235,6 +1300,8 @@ def main():
 
     # ---- phase 1: RCCL's all-gather (one GPU: the kernel alone) — timed, verified, held -------
     job, step_s, wall, info = run_job(cfg, layout, main_n, args, world, rank, dev, g_eff, gather="rccl")
+    if args.dump_outputs and rank == 0:
+        write_outputs(job.outputs, args.dump_outputs)
     check = self_check(job)
     launch_s = job_extras(job, step_s, info, args, cfg, world, dev, g_eff, main_n, backend)
     cpu = None
@@ -1298,7 +1365,7 @@ def main():
                     log(f"[rank {rank}] auditing {AUDIT_STEPS} more steps of the {pg_name} gather ...")
                     paudit = push_audit(pjob, world, dev)
                     pinfo["push_audit"] = paudit
-                    pcheck = self_check(pjob)
+                    pcheck = self_check(pjob, gates_adoption=True)
                     if not paudit["verified"]:
                         status = "failed_self_check"
                         pinfo["push_failed_self_check"] = {"gather": pg_name, "audit": paudit,
@@ -1342,6 +1409,8 @@ def main():
                 job.release()
                 job, step_s, wall, info, check = pjob, pstep, pwall, {**info, **pinfo}, pcheck
                 gather_main = pg_name
+                if args.dump_outputs and rank == 0:  # the line's job is now the push job: its outputs
+                    write_outputs(job.outputs, args.dump_outputs)
                 launch_s = job_extras(job, step_s, info, args, cfg, world, dev, g_eff, main_n, backend)
                 phases = line["multi_gpu"]["phases"]
                 trials = line["multi_gpu"].get("plan_trials")

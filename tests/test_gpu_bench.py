@@ -29,7 +29,7 @@ def _rehearse(config, extra=(), inject=None):
         env["FLEARN_BENCH_INJECT"] = inject
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(REPO / "bench.py"), "--gpus", "2",
-           "--steps", "3", "--warmup", "1", "--config", config, *extra]
+           "--full", "--steps", "3", "--warmup", "1", "--config", config, *extra]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=str(REPO))
 
 
@@ -211,13 +211,54 @@ def test_bench_fails_on_a_misplaced_gather(cuda):
     assert "exitcode  : 3" in p.stderr and verify.EXIT_MISMATCH == 3  # each rank's status (torchrun exits 1)
 
 
-def test_single_gpu_line_is_verified(cuda):
-    """The default N=1 line checks its own output too (one launch, no gather)."""
-    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "3", "--warmup", "1", "--config", "c3",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=280, cwd=str(REPO))
+def test_single_gpu_line_is_verified(cuda, tmp_path):
+    """The N=1 line of a --full run checks its own output too (one launch, no gather); --dump-outputs
+    writes the fused step's model and state, sampled (25.6 M columns > 4 Mi)."""
+    import numpy as np
+
+    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--config", "c3",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=280, cwd=str(REPO))
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["full"] is True
     assert d["verify"]["verified"] is True and d["verify"]["windows"] >= 64 and d["verify"]["state_windows"] >= 2
+    w, v = np.load(tmp_path / "w_glob.npy"), np.load(tmp_path / "v_t.npy")
+    assert (w.dtype, v.dtype) == (np.float32, np.float64) and w.shape == v.shape == (4 * 1024 * 1024,)
+    assert np.isfinite(w).all() and np.isfinite(v).all() and np.abs(v).max() > 0
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(cuda, tmp_path):
+    """A plain run (no --full) times its steps and prints the line: no self-check, no CPU baseline;
+    --steps sets the timed steps; --dump-outputs DIR writes the last timed step's global model,
+    here whole (44,426 columns), bit-equal to the same kernel's reduce of the same seeded uploads."""
+    import numpy as np
+    import torch
+
+    import bench
+    from flearn_amd import _native as na
+    from flearn_amd import aggregator as agg
+    from flearn_amd import layouts
+
+    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--config", "c1k", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120, cwd=str(REPO))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["verify"] is None and d["cpu_baseline"] is None
+    assert d["steps"] == 4 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "GiB/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "fp32" and d["metric"] == bench.METRIC
+    assert sorted(f.name for f in (tmp_path / "out").iterdir()) == ["w_glob.npy"]
+    got = np.load(tmp_path / "out" / "w_glob.npy")
+    n, cols = 1000, layouts.fp32_elems(layouts.get("lenet5"))
+    assert got.dtype == np.float32 and got.shape == (cols,)
+    x = torch.empty((n, -(-cols // bench.ALIGN) * bench.ALIGN), dtype=torch.float32, device=cuda)  # 16-B aligned rows
+    agg.fill_uniform(x, seed=bench.UPLOAD_SEED, n_cols=cols)
+    want = torch.empty(cols, dtype=torch.float32, device=cuda)
+    agg.reduce_stack(x, torch.ones(n, dtype=torch.float32, device=cuda), na.MODE_W32_DIV64, float(n), n_cols=cols, out32=want)
+    assert got.tobytes() == want.cpu().numpy().tobytes()
 
 
 @pytest.mark.timeout(300)

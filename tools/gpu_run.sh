@@ -6,7 +6,7 @@
 # time limit and the steps are chained: the first failure ends the call (no retries).
 #
 #   suite          pytest -m gpu (whole suite), smoke(), the default bench line   (the driver's round end)
-#   bench          the default bench line (ARGS are passed to bench.py)
+#   bench          the default bench line with every extra (bench.py --full; ARGS are passed to it)
 #   rehearsal      bench.py's N>1 path: ranks sharing the GPU over gloo (ARGS: config ranks [bench flags],
 #                  default ns 2)
 #   profile        per config (ARGS: tag:config[:flags] ..., default ns:ns): bench line, bench under
@@ -47,7 +47,7 @@ suite() {
 }
 
 bench() {
-  timeout -k 10 300 python3 bench.py "$@" > "$O/bench.json" 2> "$O/bench.err" || { echo "bench failed"; tail "$O/bench.err"; return 1; }
+  timeout -k 10 300 python3 bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err" || { echo "bench failed"; tail "$O/bench.err"; return 1; }
   cat "$O/bench.json"
 }
 
@@ -55,7 +55,7 @@ rehearsal() {
   local cfg=${1:-ns} g=${2:-2}
   if [ $# -ge 2 ]; then shift 2; else set --; fi
   FLEARN_BENCH_BACKEND=gloo MASTER_ADDR=127.0.0.1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node="$g" --master-addr=127.0.0.1 --master-port=29533 bench.py --gpus "$g" --steps 5 --warmup 2 \
+    --nproc-per-node="$g" --master-addr=127.0.0.1 --master-port=29533 bench.py --gpus "$g" --full --steps 5 --warmup 2 \
     --config "$cfg" "$@" > "$O/rehearsal_${cfg}_g$g.json" 2> "$O/rehearsal_${cfg}_g$g.err" \
     || { echo "rehearsal failed"; tail "$O/rehearsal_${cfg}_g$g.err"; return 1; }
   echo "rehearsal $cfg g$g ok"
@@ -68,7 +68,7 @@ profile() {
   for e in "${entries[@]}"; do
     IFS=: read -r tag cfg flags <<< "$e"
     flags=${flags//,/ }
-    timeout -k 10 300 python3 bench.py --config "$cfg" $flags > "$O/bench_$tag.json" 2> "$O/bench_$tag.err" || return 1
+    timeout -k 10 300 python3 bench.py --full --config "$cfg" $flags > "$O/bench_$tag.json" 2> "$O/bench_$tag.err" || return 1
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_$tag" -o "$tag" -- \
       python3 "$R/bench.py" --config "$cfg" $flags --no-cpu-baseline --no-verify > "$O/trace_${tag}_bench.json" 2> "$O/trace_$tag.err" || return 1
     timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch_$tag" -o "$tag" -- \

@@ -1,7 +1,8 @@
 // fa_device.hpp — device code of the FedAVG-family aggregation engine (gfx950).
 //
-// Included by fa_reduce.hip (the product C ABI) and by tools/tune_reduce.hip (the geometry
-// sweep).  Everything here is header-only templates in namespace fa.
+// Included by fa_reduce.hip (the product C ABI): every kernel here is one the product launches.
+// The tuning tools include it through tools/fa_tune_device.hpp, which adds the kernels only they
+// launch.  Everything here is header-only templates in namespace fa.
 //
 // Hot path: Strategy.server_ensemble (flearn/common/strategy/strategy.py:102-130), i.e. for
 // every element p of the flattened model bucket
@@ -153,6 +154,36 @@ __device__ __forceinline__ T update(const Epi<T>& e, T g, T l, T& vv) {
   }
 }
 
+// divide and update one quad: a = its sums, l / vv = its loaded state in, updated state out (l:
+// FedDyn's h), w = the new global values
+template <typename T, int OP, typename A>
+__device__ __forceinline__ void epi_compute(const Epi<T>& e, const typename vec4<A>::type a,
+                                            typename vec4<float>::type& l, typename vec4<T>::type& vv,
+                                            typename vec4<T>::type& w) {
+  if constexpr (OP == FA_OP_DYN) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const T g = (T)a[j] / e.denom;
+      const T d = g * e.n - vv[j];                  // delta_theta = w_glob*N - theta   dyn.py:20-21
+      const float hn = (float)((T)l[j] - e.c * d);  // h -= alpha/N * delta (fp32 h)    dyn.py:26
+      const float ah = e.alpha32 * hn;              // alpha * h stays fp32              dyn.py:33
+      w[j] = g - (T)ah;                             // w_glob - alpha*h                  dyn.py:33
+      l[j] = hn;
+      vv[j] = w[j];                                 // theta = w_glob                    dyn.py:34
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const T g = (T)a[j] / e.denom;  // np.divide(w_glob, np.sum(a))  strategy.py:127-129
+      T vj = vv[j];
+      w[j] = update<T, OP>(e, g, (T)l[j], vj);
+      vv[j] = vj;
+    }
+  }
+}
+
+// One quad through guarded generic loads and stores (the 8-byte kinds, the ragged window end, the
+// standalone update): the arithmetic is epi_compute's.
 template <typename T, int OP, typename A>
 __device__ __forceinline__ void finish_quad(const Epi<T>& e, int64_t c, int valid,
                                             typename vec4<A>::type acc) {
@@ -169,27 +200,8 @@ __device__ __forceinline__ void finish_quad(const Epi<T>& e, int64_t c, int vali
       vv = load_quad_guarded(e.v + c, valid);
     }
   }
-  if constexpr (OP == FA_OP_DYN) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const T g = (T)acc[j] / e.denom;
-      const T d = g * e.n - vv[j];                // delta_theta = w_glob*N - theta   dyn.py:20-21
-      const float hn = (float)((T)l[j] - e.c * d);  // h -= alpha/N * delta (fp32 h)    dyn.py:26
-      const float ah = e.alpha32 * hn;            // alpha * h stays fp32              dyn.py:33
-      w[j] = g - (T)ah;                           // w_glob - alpha*h                  dyn.py:33
-      l[j] = hn;
-      vv[j] = w[j];                               // theta = w_glob                    dyn.py:34
-    }
-    store_quad<float>(e.h + c, l, valid);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const T g = (T)acc[j] / e.denom;  // np.divide(w_glob, np.sum(a))  strategy.py:127-129
-      T vj = vv[j];
-      w[j] = update<T, OP>(e, g, (T)l[j], vj);
-      vv[j] = vj;
-    }
-  }
+  epi_compute<T, OP, A>(e, acc, l, vv, w);
+  if constexpr (OP == FA_OP_DYN) store_quad<float>(e.h + c, l, valid);
   if constexpr (OP != FA_OP_MEAN) store_quad<T>((e.v_out ? e.v_out : e.v) + c, vv, valid);
   if (e.out32) {
     typename vec4<float>::type o = {(float)w[0], (float)w[1], (float)w[2], (float)w[3]};
@@ -270,12 +282,11 @@ __device__ __forceinline__ void reduce_subtile(const typename P::x_t* __restrict
     if (PART == kFull || v < nv) finish_quad<T, OP, A>(e, (q0 + (int64_t)v * kThreads) * 4, 4, acc[v]);
 }
 
-// Buffer-descriptor form of a sub-tile (4-byte elements).  Per client row the block builds a
-// buffer resource whose base is the row's first quad of this sub-tile and whose num_records is
-// the sub-tile's valid byte count; lane offsets (VGPR) are the same for every row and slot v's
-// 4-KiB step rides in soffset.  Slots past the valid range are dropped by the hardware range
-// check (they return 0, generate no memory request and need no branch), so a partial sub-tile
-// issues exactly the loads of its valid quads with the same instruction stream as a full one.
+// Buffer descriptors (4-byte elements).  Per client row a block builds a buffer resource whose
+// base is the row's first quad of its piece and whose num_records is the piece's valid byte
+// count; lane offsets (VGPR) are the same for every row.  Accesses past the valid range are
+// dropped by the hardware range check (they return 0, generate no memory request and need no
+// branch), so a partial piece runs the same instruction stream as a full one.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* base, uint32_t bytes) {
@@ -302,25 +313,19 @@ __device__ __forceinline__ vec4<float>::type buf_load_quad(__amdgpu_buffer_rsrc_
 // Non-temporal stores: +1.6% on 100 x 25.6 M mean, +1.2% AVGM, +-0.1% Adagrad 100 x 86.6 M (5
 // interleaved passes each, tools/gpu_epi_aux2.sh, profiles/r02/tune_epiaux/); non-temporal state
 // loads were mixed (-1..-5% Adagrad) and stay cached.
-#ifndef FA_EPI_LOAD_AUX
-#define FA_EPI_LOAD_AUX 0
-#endif
-#ifndef FA_EPI_STORE_AUX
-#define FA_EPI_STORE_AUX 2
-#endif
+constexpr int kEpiLoadAux = 0;
+constexpr int kEpiStoreAux = 2;
 // 8-byte elements (v_t / theta state in f64, the f64 result) are stored as two 16-B halves per
 // quad, each instruction covering every other 16 B of a wave's 2 KiB: partial 128-B lines.
-#ifndef FA_EPI_STORE64_AUX
-#define FA_EPI_STORE64_AUX FA_EPI_STORE_AUX
-#endif
+constexpr int kEpiStore64Aux = kEpiStoreAux;
 template <typename T>
 __device__ __forceinline__ typename vec4<T>::type buf_load_tquad(__amdgpu_buffer_rsrc_t r, int q) {
   if constexpr (sizeof(T) == 4) {
-    return __builtin_bit_cast(typename vec4<T>::type, __builtin_amdgcn_raw_buffer_load_b128(r, q * 16, 0, FA_EPI_LOAD_AUX));
+    return __builtin_bit_cast(typename vec4<T>::type, __builtin_amdgcn_raw_buffer_load_b128(r, q * 16, 0, kEpiLoadAux));
   } else {
     typedef double d2 __attribute__((ext_vector_type(2)));
-    const d2 lo = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, q * 32, 0, FA_EPI_LOAD_AUX));
-    const d2 hi = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, q * 32 + 16, 0, FA_EPI_LOAD_AUX));
+    const d2 lo = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, q * 32, 0, kEpiLoadAux));
+    const d2 hi = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(r, q * 32 + 16, 0, kEpiLoadAux));
     return typename vec4<T>::type{lo[0], lo[1], hi[0], hi[1]};
   }
 }
@@ -329,16 +334,13 @@ __device__ __forceinline__ typename vec4<T>::type buf_load_tquad(__amdgpu_buffer
 // LDS so that each of the two store instructions writes 1 KiB contiguous (eight whole 128-B
 // lines) instead of every other 16 B of the 2 KiB (DESIGN.md §4 finding 22).  Callers run it
 // wave-convergent with q = (the wave's first quad) + lane (finish_piece's slots).  The product
-// enables it where it does not make the kernel spill (rowmajor_group); FA_EPI_STORE64_LDS=1
-// forces it everywhere (tuning builds).
-#ifndef FA_EPI_STORE64_LDS
-#define FA_EPI_STORE64_LDS 0
-#endif
+// enables it where it does not make the kernel spill (reduce_kernel_rowmajor's XL,
+// reduce_kernel_segrows_rm's XLS).
 template <typename T, bool XL = false>
 __device__ __forceinline__ void buf_store_tquad(__amdgpu_buffer_rsrc_t r, int q, typename vec4<T>::type v) {
   if constexpr (sizeof(T) == 4) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, q * 16, 0, FA_EPI_STORE_AUX);
-  } else if constexpr (XL || FA_EPI_STORE64_LDS != 0) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, q * 16, 0, kEpiStoreAux);
+  } else if constexpr (XL) {
     typedef double d2 __attribute__((ext_vector_type(2)));
     __shared__ d2 xch[8][128];  // 2 KiB per wave, up to 8 waves per block
     // the thread index made opaque HERE: otherwise the lane-dependent LDS and store addresses
@@ -356,16 +358,16 @@ __device__ __forceinline__ void buf_store_tquad(__amdgpu_buffer_rsrc_t r, int q,
     __builtin_amdgcn_wave_barrier();
     const d2 a = s[lane], b = s[64 + lane];
     const int base = (q - lane) * 32;  // the wave's first byte
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, a), r, base + lane * 16, 0, FA_EPI_STORE64_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, a), r, base + lane * 16, 0, kEpiStore64Aux);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, b), r, base + 1024 + lane * 16, 0,
-                                           FA_EPI_STORE64_AUX);
+                                           kEpiStore64Aux);
     __builtin_amdgcn_wave_barrier();  // the next slot's writes come after these reads
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
   } else {
     typedef double d2 __attribute__((ext_vector_type(2)));
     const d2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), r, q * 32, 0, FA_EPI_STORE64_AUX);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), r, q * 32 + 16, 0, FA_EPI_STORE64_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), r, q * 32, 0, kEpiStore64Aux);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), r, q * 32 + 16, 0, kEpiStore64Aux);
   }
 }
 
@@ -409,34 +411,6 @@ __device__ __forceinline__ void epi_load(const EpiRsrc<T, OP>& r, int q, typenam
   }
 }
 
-// divide and update one quad: a = its sums, l / vv = its loaded state in, updated state out (l:
-// FedDyn's h), w = the new global values
-template <typename T, int OP, typename A>
-__device__ __forceinline__ void epi_compute(const Epi<T>& e, const typename vec4<A>::type a,
-                                            typename vec4<float>::type& l, typename vec4<T>::type& vv,
-                                            typename vec4<T>::type& w) {
-  if constexpr (OP == FA_OP_DYN) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const T g = (T)a[j] / e.denom;
-      const T d = g * e.n - vv[j];                  // delta_theta = w_glob*N - theta   dyn.py:20-21
-      const float hn = (float)((T)l[j] - e.c * d);  // h -= alpha/N * delta (fp32 h)    dyn.py:26
-      const float ah = e.alpha32 * hn;              // alpha * h stays fp32              dyn.py:33
-      w[j] = g - (T)ah;                             // w_glob - alpha*h                  dyn.py:33
-      l[j] = hn;
-      vv[j] = w[j];                                 // theta = w_glob                    dyn.py:34
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const T g = (T)a[j] / e.denom;  // np.divide(w_glob, np.sum(a))  strategy.py:127-129
-      T vj = vv[j];
-      w[j] = update<T, OP>(e, g, (T)l[j], vj);
-      vv[j] = vj;
-    }
-  }
-}
-
 // store quad q's updated state and results.  GUARD = false: the result stores are issued
 // unconditionally (a null out32 / out64 has an empty descriptor range, so they are dropped) and
 // the quad is one basic block.
@@ -477,62 +451,6 @@ __device__ __forceinline__ void finish_piece(const Epi<T>& e, int64_t qbase, int
   }
 }
 
-template <class P, typename T, int OP, int V, int U, bool NT>
-__device__ __forceinline__ void reduce_subtile_buf(const float* __restrict__ base, int64_t stride,
-                                                   int n, const typename P::w_t* __restrict__ w,
-                                                   int64_t qt, int nvalid_quads, const Epi<T>& e) {
-  typedef typename P::acc_t A;
-  typedef typename vec4<float>::type XV;
-  typedef typename vec4<A>::type AV;
-  const char* tile0 = reinterpret_cast<const char*>(base + qt * 4);
-  const uint32_t bytes = (uint32_t)nvalid_quads * 16u;
-  const int64_t row_bytes = stride * 4;
-  const int voff = (int)threadIdx.x * 16;
-  AV acc[V];
-  {
-    const __amdgpu_buffer_rsrc_t r = row_rsrc(tile0, bytes);
-    const typename P::w_t w0 = w[0];
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const XV x = buf_load_quad<NT>(r, voff, v * kThreads * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[v][j] = P::mul(w0, x[j]);
-    }
-  }
-  int i = 1;
-  for (; i + U <= n; i += U) {
-    XV x[U][V];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const __amdgpu_buffer_rsrc_t r = row_rsrc(tile0 + (int64_t)(i + u) * row_bytes, bytes);
-#pragma unroll
-      for (int v = 0; v < V; ++v) x[u][v] = buf_load_quad<NT>(r, voff, v * kThreads * 16);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const typename P::w_t wu = w[i + u];
-#pragma unroll
-      for (int v = 0; v < V; ++v)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[v][j] = add<A>(acc[v][j], P::mul(wu, x[u][v][j]));
-    }
-  }
-  for (; i < n; ++i) {
-    const __amdgpu_buffer_rsrc_t r = row_rsrc(tile0 + (int64_t)i * row_bytes, bytes);
-    const typename P::w_t wi = w[i];
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      const XV x = buf_load_quad<NT>(r, voff, v * kThreads * 16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[v][j] = add<A>(acc[v][j], P::mul(wi, x[j]));
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < V; ++v)
-    if (v * kThreads + (int)threadIdx.x < nvalid_quads)
-      finish_quad<T, OP, A>(e, (qt + (int64_t)v * kThreads + threadIdx.x) * 4, 4, acc[v]);
-}
-
 // The window's ragged end (at most one wave per launch): one quad at a time, element-guarded.
 template <class P, typename T, int OP>
 __device__ __attribute__((noinline)) void reduce_ragged(const typename P::x_t* __restrict__ base,
@@ -564,7 +482,7 @@ __device__ __attribute__((noinline)) void reduce_ragged(const typename P::x_t* _
 }
 
 // Sub-tile starting at quad qt, limited to quads < qlim (the block's range, <= the window).
-template <class P, typename T, int OP, int V, int U, bool NT, bool BUF = false>
+template <class P, typename T, int OP, int V, int U, bool NT>
 __device__ __forceinline__ void reduce_range_subtile(const typename P::x_t* __restrict__ base,
                                                      int64_t stride, int n,
                                                      const typename P::w_t* __restrict__ w,
@@ -573,16 +491,6 @@ __device__ __forceinline__ void reduce_range_subtile(const typename P::x_t* __re
   constexpr int kSub = kThreads * V;
   const int64_t q0 = qt + threadIdx.x;
   const int64_t qfull = ncols / 4;  // complete quads in the window
-  if constexpr (BUF) {
-    static_assert(sizeof(typename P::x_t) == 4, "buffer path is for 4-byte elements");
-    const int64_t end = qt + kSub < qlim ? qt + kSub : qlim;  // this sub-tile's quads [qt, end)
-    const int64_t full_end = end < qfull ? end : qfull;
-    if (full_end > qt) reduce_subtile_buf<P, T, OP, V, U, NT>(base, stride, n, w, qt, (int)(full_end - qt), e);
-    // the window's ragged last quad (ncols % 4 != 0), if it falls in this sub-tile
-    if (qfull < end && qfull >= qt && q0 == qt + (qfull - qt) % kThreads)
-      reduce_ragged<P, T, OP>(base, stride, n, w, qfull, qfull + 1, ncols, e);
-    return;
-  }
   if (qt + kSub <= qlim && qt + kSub <= qfull) {
     reduce_subtile<P, T, OP, V, U, NT, kFull>(base, stride, n, w, q0, V, e);
     return;
@@ -605,7 +513,7 @@ __device__ __forceinline__ void reduce_range_subtile(const typename P::x_t* __re
 // blocks of a round finish together (no tail of late blocks) and, because neighbouring blocks own
 // neighbouring column ranges and sweep the rows in lockstep, the chip streams each client row
 // almost sequentially — the access pattern of a plain linear read.
-template <class P, typename T, int OP, int V, int U, bool NT, bool BUF = false>
+template <class P, typename T, int OP, int V, int U, bool NT>
 __global__ __launch_bounds__(kThreads) void reduce_kernel_balanced(
     const typename P::x_t* __restrict__ stack, int64_t stride, int n,
     const typename P::w_t* __restrict__ w, int64_t col0, int64_t ncols, Epi<T> e) {
@@ -618,19 +526,7 @@ __global__ __launch_bounds__(kThreads) void reduce_kernel_balanced(
   const int64_t qlim = c1 * 64 < nquads ? c1 * 64 : nquads;
   const typename P::x_t* base = stack + col0;
   for (int64_t qt = c0 * 64; qt < qlim; qt += kThreads * V)
-    reduce_range_subtile<P, T, OP, V, U, NT, BUF>(base, stride, n, w, qt, qlim, ncols, e);
-}
-
-// One sub-tile per block (grid = number of sub-tiles): the simple mapping.
-template <class P, typename T, int OP, int V, int U, bool NT, bool BUF = false>
-__global__ __launch_bounds__(kThreads) void reduce_kernel(
-    const typename P::x_t* __restrict__ stack, int64_t stride, int n,
-    const typename P::w_t* __restrict__ w, int64_t col0, int64_t ncols, Epi<T> e) {
-  const int64_t qt = (int64_t)blockIdx.x * (kThreads * V);
-  const int64_t nquads = (ncols + 3) / 4;
-  reduce_range_subtile<P, T, OP, V, U, NT, BUF>(stack + col0, stride, n, w, qt,
-                                           qt + kThreads * V < nquads ? qt + kThreads * V : nquads,
-                                           ncols, e);
+    reduce_range_subtile<P, T, OP, V, U, NT>(base, stride, n, w, qt, qlim, ncols, e);
 }
 
 // acc + w*x on whole quads, written as <4 x T> IR operations: per-element scalar code gets packed
@@ -769,53 +665,6 @@ __device__ __forceinline__ void rows_piece(const float* __restrict__ stack, int6
   }
 }
 
-// Segmented row-pointer reduce (fa_reduce_f32_rows): uploads that are separate device tensors
-// per (client, key) are read where they lie — no pack copy.  Work = pieces (fa_rows_plan): each
-// is a column range of ONE segment, so every row of a piece is one contiguous range of one
-// tensor and gets one buffer descriptor; client order and epilogue are the row pipeline's.
-//   * scheduling: pieces come largest first; block b starts with piece b and then claims the
-//     next unclaimed one from a device counter.  Blocks finish within about one small piece of
-//     each other whatever the mix of tensor sizes — a static split of 100 ResNet-sized uploads
-//     left a ~10% tail (tools/tune_rows.py);
-//   * narrow pieces (<= W KiB of a row: BN vectors, biases) are latency-bound, not
-//     bandwidth-bound: they take a one-quad-per-lane sweep V*D rows deep instead of D, so a
-//     64-element tensor of 100 clients costs ~7 HBM round trips instead of ~50.
-// The counter must be 0 at launch (the host clears it on the stream before each launch).
-template <class P, typename T, int OP, int V, int D, int W, bool NT>
-__global__ __launch_bounds__(64 * W) void reduce_kernel_segrows(const float* const* __restrict__ rows, int n,
-                                                                const typename P::w_t* __restrict__ w,
-                                                                const fa_piece* __restrict__ pieces,
-                                                                int64_t npieces, int* __restrict__ next, Epi<T> e) {
-  typedef typename P::acc_t A;
-  typedef typename vec4<A>::type AV;
-  __shared__ int s_next;
-  int64_t p = blockIdx.x;
-  while (p < npieces) {
-    int claimed = 0;
-    if (threadIdx.x == 0) claimed = (int)gridDim.x + atomicAdd(next, 1);
-    const fa_piece pc = pieces[p];
-    const float* const* rp = rows + (int64_t)pc.seg * n;
-    // a segment's ragged last quad rides in the vector path: the range check is per dword
-    // (`bytes` = exactly the piece's columns), its missing elements load as 0 and are not stored
-    const int nq = (pc.n_cols + 3) >> 2;
-    const uint32_t bytes = (uint32_t)pc.n_cols * 4u;
-    const PtrRows row{rp, pc.seg_off * 4};
-    if (nq > 64 * W) {
-      AV acc[V];
-      rows_sweep<P, V, D, W, NT>(row, bytes, n, w, acc);
-      finish_piece<T, OP, A, V, 64 * W, (V >= 2 ? 2 : V)>(e, pc.col / 4, pc.n_cols, acc);
-    } else if (nq > 0) {
-      AV acc[1];
-      rows_sweep<P, 1, V * D, W, NT>(row, bytes, n, w, acc);
-      finish_piece<T, OP, A, 1, 64 * W, 1>(e, pc.col / 4, pc.n_cols, acc);
-    }
-    if (threadIdx.x == 0) s_next = claimed;
-    __syncthreads();
-    p = s_next;
-    __syncthreads();  // s_next is rewritten in the next iteration
-  }
-}
-
 // Split-N reduce (fa_reduce_f32_splitn) for windows too narrow to fill the chip with one
 // sequential sweep per column (LeNet5-sized models of many clients: 44 K columns x 1000 rows is
 // 174 one-KiB row chunks for 256 CUs, each walking 1000 rows).  Here the CLIENTS are split too:
@@ -832,7 +681,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_segrows(const float* con
 // sum): those are re-summed in list order by wave 0 (the cancellation guard below), bit-exact.
 // oracle.c_reduce_splitn restates this exact order and guard (the tests pin it bit for bit).
 // Needs n >= W (every split non-empty; the host falls back to the sequential kernel otherwise).
-template <class P, typename T, int OP, int W, int D, bool NT, bool STRIDED = false>
+template <class P, typename T, int OP, int W, int D, bool NT>
 __global__ __launch_bounds__(64 * W) void reduce_kernel_splitn(const float* __restrict__ stack, int64_t stride, int n,
                                                                const typename P::w_t* __restrict__ w, int64_t col0,
                                                                int64_t ncols, Epi<T> e) {
@@ -849,11 +698,9 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_splitn(const float* __re
   const int64_t cleft = ncols - qb * 4;
   const int tcols = cleft <= 0 ? 0 : (cleft < 256 ? (int)cleft : 256);
   const int nq = (tcols + 3) / 4;  // quads, the last possibly partial
-  // split wv: contiguous rows [r0, r1), or (STRIDED) rows wv, wv+W, wv+2W, ... so that all
-  // splits read neighbouring rows at the same time
-  const int r0 = STRIDED ? wv : (int)((int64_t)wv * n / W);
-  const int r1 = STRIDED ? n : (int)((int64_t)(wv + 1) * n / W);
-  constexpr int RS = STRIDED ? W : 1;  // row step of a split
+  // split wv: contiguous rows [r0, r1)
+  const int r0 = (int)((int64_t)wv * n / W);
+  const int r1 = (int)((int64_t)(wv + 1) * n / W);
   typedef typename vec4<float>::type XV;
   const char* tile00 = reinterpret_cast<const char*>(stack + col0 + qb * 4);
   const uint32_t bytes = (uint32_t)tcols * 4u;
@@ -868,8 +715,8 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_splitn(const float* __re
     // product p = fl(w*x) feeds the running sum (acc + p: the same rounding as acc + w*x, no
     // contraction) and the running sum of |p|
     const char* tile0 = tile00 + (int64_t)r0 * stride * 4;
-    const int64_t row_bytes = stride * 4 * RS;
-    const int cnt = (r1 - r0 + RS - 1) / RS;  // >= 1
+    const int64_t row_bytes = stride * 4;
+    const int cnt = r1 - r0;  // >= 1
     const typename P::w_t* ws = w + r0;
     XV x[D];
 #pragma unroll
@@ -883,7 +730,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_splitn(const float* __re
     }
 #pragma unroll
     for (int d = 1; d < D; ++d) {  // rows 1..D-1
-      const AV p = quad_mul<P>(ws[(d < cnt ? d : 0) * RS], x[d]);
+      const AV p = quad_mul<P>(ws[d < cnt ? d : 0], x[d]);
       acc = d < cnt ? acc + p : acc;
       aacc = d < cnt ? aacc + absq(p) : aacc;
       __builtin_amdgcn_sched_barrier(0);
@@ -895,7 +742,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_splitn(const float* __re
 #pragma unroll
       for (int d = 0; d < D; ++d) {
         const int i = base + d;
-        const AV p = quad_mul<P>(ws[(i < cnt ? i : 0) * RS], x[d]);
+        const AV p = quad_mul<P>(ws[i < cnt ? i : 0], x[d]);
         acc = i < cnt ? acc + p : acc;
         aacc = i < cnt ? aacc + absq(p) : aacc;
         __builtin_amdgcn_sched_barrier(0);
@@ -941,43 +788,34 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_splitn(const float* __re
   }
 }
 
-// Row-major form of the row-pointer reduce.  A claim is a GROUP of KG wide pieces (the leading
-// pieces[0].aux entries of the largest-first table) swept together row by row — step (row i,
-// piece j), j fastest, one step (V*W KiB) in flight, like reduce_kernel_rowmajor — so the blocks
-// stay on neighbouring client rows as the stack kernel's do; the row pointer of the step after
-// the next one is fetched while the next is in flight (every index is static: j is unrolled).
-// Claims past the groups are the narrow pieces, one at a time, through the deep one-quad sweep.
+// Segmented row-pointer reduce (fa_reduce_f32_rows): uploads that are separate device tensors
+// per (client, key) are read where they lie — no pack copy.  Work = pieces (fa_rows_plan): each
+// is a column range of ONE segment, so every row of a piece is one contiguous range of one
+// tensor and gets one buffer descriptor; client order and epilogue are the row pipeline's.
+//   * a claim is a GROUP of KG wide pieces (the leading pieces[0].aux entries of the
+//     largest-first table) swept together row by row — step (row i, piece j), j fastest, one step
+//     (V*W KiB) in flight, like reduce_kernel_rowmajor — so the blocks stay on neighbouring client
+//     rows as the stack kernel's do; the row pointer of the step after the next one is fetched
+//     while the next is in flight (every index is static: j is unrolled);
+//   * scheduling: block b starts with claim b and then takes the next unclaimed one from a device
+//     counter.  Blocks finish within about one small piece of each other whatever the mix of
+//     tensor sizes — a static split of 100 ResNet-sized uploads left a ~10% tail
+//     (tools/tune_rows.py);
+//   * claims past the groups are the narrow pieces (<= W KiB of a row: BN vectors, biases), one at
+//     a time.  They are latency-bound, not bandwidth-bound, and take a one-quad-per-lane sweep DN
+//     rows deep, so a 64-element tensor of 100 clients costs ~7 HBM round trips instead of ~50.
+// The counter must be 0 at launch (the host clears it on the stream before each launch).
 // TR (tools/tune_rows.hip): wave 0 of every block stamps the 100-MHz wall clock at each claim it
 // starts (e.trace[block * 32 + 1 + c], c < 30) and at its exit (slot 0), claim count in slot 31.
-// DS: steps in flight (1, or any divisor of KG: step s = (i, j) lives in slot j % DS).
-// PFA > 0 (tuning, tools/tune_rows.hip): translation prefetch — after each refill every wave also
-// loads ONE dword (all lanes the same address) of the step PFA steps past the next one, so the
-// page translation of that upload row is resolved before its 64-KiB step is issued (the
-// row-pointer kernel takes 2.4x the UTCL1 translation misses of the stack kernel on per-tensor
-// allocations: profiles/r04/rows_pmc/).  The dword is consumed one row later (xor into a sink
-// kept alive by an empty asm), when it has long arrived.
-// LT > 0 (n <= LT clients, the host's choice): the group's KG x n row pointers are copied into LDS
-// at its claim (one coalesced vector load per wave, one barrier) and every step's pointer comes
-// from there (a ds_read, made wave-uniform with readfirstlane) instead of a scalar load from the
-// rows table in L2: 8 waves x 2 pointer loads per step, each a scalar-cache miss on a table of
-// S x N pointers, left the waves waiting on SMEM before their vector loads (SQ_INSTS_SMEM 9.2x,
-// SQ_WAIT_INST_ANY 3-4x the stack kernel's: profiles/r04/rows_pmc/).
-template <int LT>
-__device__ __forceinline__ const float* srm_row_ptr(const float* const* lds_row, const float* const* g_row, int i) {
-  if constexpr (LT > 0) {
-    const uint64_t p = reinterpret_cast<uint64_t>(lds_row[i]);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-    return reinterpret_cast<const float*>(((uint64_t)hi << 32) | lo);
-  } else {
-    return g_row[i];
-  }
-}
-
 // XLS: the epilogue's f64 stores as whole cache lines (buf_store_tquad XL, 2 KiB of LDS per wave),
 // as rowmajor_group does for fused epilogues at KG <= 3 (DESIGN.md §4 finding 22).
-template <class P, typename T, int OP, int V, int W, int KG, int DN, bool NT, bool TR = false, int DS = 1,
-          bool SG = false, int PFA = 0, int LT = 0, bool XLS = false>
+// Dead ends, measured and removed (profiles/HISTORY.md §4, "row-pointer" findings):
+//   * one claimed piece at a time, column-major (kept in tools/fa_tune_device.hpp): finding 4;
+//   * two or more steps in flight: finding 8;
+//   * static groups in lockstep, claiming only the narrow pieces: finding 9;
+//   * a one-dword translation prefetch some steps ahead: finding 11;
+//   * the group's row pointers staged in LDS: §10 item 4.
+template <class P, typename T, int OP, int V, int W, int KG, int DN, bool NT, bool TR = false, bool XLS = false>
 __global__ __launch_bounds__(64 * W) void reduce_kernel_segrows_rm(const float* const* __restrict__ rows, int n,
                                                                    const typename P::w_t* __restrict__ w,
                                                                    const fa_piece* __restrict__ pieces,
@@ -992,11 +830,8 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_segrows_rm(const float* 
   const int voff = (int)threadIdx.x * 16;
   int64_t t = blockIdx.x;
   int nclaim = 0;
-  // SG (static groups, tuning): block b takes groups b, b + grid, ... in lockstep and claims only
-  // the narrow pieces, numbered from max(groups, grid)
-  const int64_t nbase = SG && groups > (int64_t)gridDim.x ? groups : (int64_t)gridDim.x;
-#define FA_SRM_CLAIM() \
-  ((SG && t < groups && t + (int64_t)gridDim.x < groups) ? (int)(t + gridDim.x) : (int)nbase + atomicAdd(next, 1))
+  const int64_t nbase = gridDim.x;  // claims are numbered from the grid's size on
+#define FA_SRM_CLAIM() ((int)nbase + atomicAdd(next, 1))
   while (t < claims) {
     // the next claim: a group (hundreds of us) claims during its last row, so an idle block can
     // take what is left meanwhile (claiming at the start reserved work behind a long group while
@@ -1023,43 +858,27 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_segrows_rm(const float* 
         cols[j] = pc.n_cols;
         bytes[j] = (uint32_t)pc.n_cols * 4u;
       }
-      __shared__ const float* s_tab[KG][LT > 0 ? LT : 1];
-      if constexpr (LT > 0) {  // the previous claim's readers are past the loop-end barriers
-#pragma unroll
-        for (int j = 0; j < KG; ++j)
-          for (int k = (int)threadIdx.x; k < n; k += 64 * W) s_tab[j][k] = rp[j][k];
-        __syncthreads();
-      }
       // row pointer of step (i, j); rows clamped (a step past the end is never loaded)
-#define FA_SRM_PTR(i, j) (reinterpret_cast<const char*>(srm_row_ptr<LT>(s_tab[j], rp[j], (i) < n ? (i) : n - 1)) + ob[j])
-#define FA_SRM_LOAD(p, j, slot)                                                                              \
-  {                                                                                                          \
-    const __amdgpu_buffer_rsrc_t r_ = row_rsrc((p), bytes[j]);                                               \
-    _Pragma("unroll") for (int v = 0; v < V; ++v) x[slot][v] = buf_load_quad<NT>(r_, voff + v * 64 * W * 16, 0); \
+#define FA_SRM_PTR(i, j) (reinterpret_cast<const char*>(rp[j][(i) < n ? (i) : n - 1]) + ob[j])
+#define FA_SRM_LOAD(p, j)                                                                              \
+  {                                                                                                    \
+    const __amdgpu_buffer_rsrc_t r_ = row_rsrc((p), bytes[j]);                                         \
+    _Pragma("unroll") for (int v = 0; v < V; ++v) x[v] = buf_load_quad<NT>(r_, voff + v * 64 * W * 16, 0); \
   }
-      static_assert(KG % DS == 0, "steps in flight must divide the group");
       AV acc[KG][V];
-      XV x[DS][V];
-      uint32_t pf[KG > 0 ? KG : 1];
-      uint32_t sink = 0;
-#pragma unroll
-      for (int j = 0; j < KG; ++j) pf[j] = 0;
-#pragma unroll
-      for (int d = 0; d < DS; ++d) FA_SRM_LOAD(FA_SRM_PTR(d / KG, d % KG), d % KG, d);
-      const char* pn = FA_SRM_PTR(DS / KG, DS % KG);  // the pointer of the next step to load
-      // after consuming step (i, j): refill its slot with step (i, j) + DS, then fetch the pointer
-      // of the step after that one
-#define FA_SRM_REFILL(i, j)                                                                          \
-  __builtin_amdgcn_sched_barrier(0);                                                                 \
-  if ((i) + ((j) + DS) / KG < n) {                                                                   \
-    FA_SRM_LOAD(pn, ((j) + DS) % KG, (j) % DS);                                                      \
-    pn = FA_SRM_PTR((i) + ((j) + DS + 1) / KG, ((j) + DS + 1) % KG);                                \
-    if constexpr (PFA > 0) {                                                                         \
-      sink ^= pf[j];                                                                                 \
-      pf[j] = __builtin_amdgcn_raw_buffer_load_b32(                                                  \
-          row_rsrc(FA_SRM_PTR((i) + ((j) + DS + 1 + PFA) / KG, ((j) + DS + 1 + PFA) % KG), 4u), 0, 0, 0); \
-    }                                                                                                \
-  }                                                                                                  \
+      XV x[V];
+      // the first step.  (A one-trip loop on purpose: written as a plain statement the sweep is
+      // scheduled differently — same registers, other instruction order — and every measurement
+      // of this kernel was taken on the code this form compiles to.)
+      for (int d = 0; d < 1; ++d) FA_SRM_LOAD(FA_SRM_PTR(d, 0), 0);
+      const char* pn = FA_SRM_PTR(1 / KG, 1 % KG);  // the pointer of the next step to load
+      // after consuming step (i, j): load the next step, then fetch the pointer of the one after it
+#define FA_SRM_REFILL(i, j)                                        \
+  __builtin_amdgcn_sched_barrier(0);                               \
+  if ((i) + ((j) + 1) / KG < n) {                                  \
+    FA_SRM_LOAD(pn, ((j) + 1) % KG);                               \
+    pn = FA_SRM_PTR((i) + ((j) + 2) / KG, ((j) + 2) % KG);         \
+  }                                                                \
   __builtin_amdgcn_sched_barrier(0);
       {  // row 0: the products initialise the sums (peeled: a select between the first product
          // and the running sum kept both alive for every slot and spilled KG >= 3)
@@ -1068,7 +887,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_segrows_rm(const float* 
 #pragma unroll
         for (int j = 0; j < KG; ++j) {
 #pragma unroll
-          for (int v = 0; v < V; ++v) acc[j][v] = quad_mul<P>(w0, x[j % DS][v]);
+          for (int v = 0; v < V; ++v) acc[j][v] = quad_mul<P>(w0, x[v]);
           FA_SRM_REFILL(0, j)
         }
       }
@@ -1078,18 +897,13 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_segrows_rm(const float* 
 #pragma unroll
         for (int j = 0; j < KG; ++j) {
 #pragma unroll
-          for (int v = 0; v < V; ++v) acc[j][v] = quad_axpy<P>(acc[j][v], wi, x[j % DS][v]);
+          for (int v = 0; v < V; ++v) acc[j][v] = quad_axpy<P>(acc[j][v], wi, x[v]);
           FA_SRM_REFILL(i, j)
         }
       }
 #undef FA_SRM_REFILL
 #undef FA_SRM_LOAD
 #undef FA_SRM_PTR
-      if constexpr (PFA > 0) {
-#pragma unroll
-        for (int j = 0; j < KG; ++j) sink ^= pf[j];
-        asm volatile("" ::"v"(sink));
-      }
 #pragma unroll
       for (int j = 0; j < KG; ++j) finish_piece<T, OP, A, V, 64 * W, (V >= 2 ? 2 : V), XLS>(e, col[j] / 4, cols[j], acc[j]);
     } else {
@@ -1157,11 +971,11 @@ __global__ __launch_bounds__(kThreads) void gather_rows_f64_kernel(double* __res
 // Work split: the window's 1-KiB chunks are cut into equal pieces of pc <= W*V chunks, as many
 // as make k whole rounds of the grid (pc = ceil(chunks / (k * grid))), so every block sweeps k
 // pieces (the last one or two blocks one fewer) and the launch has no tail round.
-//   INTERLEAVE: block b takes pieces b, b+grid, b+2*grid, ...: at any moment the grid's pieces
-//               form one contiguous stretch of each row (a linear-read access pattern);
-//   otherwise:  block b takes k consecutive pieces (one contiguous share of the window).
-template <class P, typename T, int OP, int V, int D, int W, bool NT, bool INTERLEAVE = true,
-          bool XCDMAP = false>
+// Block b takes pieces b, b+grid, b+2*grid, ...: at any moment the grid's pieces form one
+// contiguous stretch of each row (a linear-read access pattern).  Dead ends (profiles/HISTORY.md):
+// k consecutive pieces per block instead (tune_reduce set "il"); consecutive piece slots for the
+// blocks that share an XCD (set "misc").
+template <class P, typename T, int OP, int V, int D, int W, bool NT>
 __global__ __launch_bounds__(64 * W) void reduce_kernel_rows(const float* __restrict__ stack,
                                                              int64_t stride, int n,
                                                              const typename P::w_t* __restrict__ w,
@@ -1173,13 +987,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_rows(const float* __rest
   const int64_t k = (chunks + g * W * V - 1) / (g * W * V);  // rounds
   const int64_t pc = (chunks + g * k - 1) / (g * k);         // chunks per piece (<= W*V)
   const int64_t pieces = (chunks + pc - 1) / pc;
-  const int64_t step = INTERLEAVE ? g : 1;
-  // XCDMAP (tuning): blocks b, b+8, b+16, ... share an XCD under round-robin placement; give
-  // them consecutive piece slots so each XCD streams one contiguous stretch per round
-  const int64_t slot = (XCDMAP && g % 8 == 0) ? (blockIdx.x % 8) * (g / 8) + blockIdx.x / 8 : blockIdx.x;
-  const int64_t first = INTERLEAVE ? slot : slot * k;
-  const int64_t last = INTERLEAVE ? pieces : (first + k < pieces ? first + k : pieces);
-  for (int64_t p = first; p < last; p += step) {
+  for (int64_t p = blockIdx.x; p < pieces; p += g) {
     const int64_t qs = p * pc * 64;
     rows_piece<P, T, OP, V, D, W, NT>(stack, stride, n, w, col0, ncols, e, qs,
                                       qs + pc * 64 < nquads ? qs + pc * 64 : nquads);
@@ -1297,14 +1105,11 @@ __device__ __forceinline__ void rowmajor_piece_geom(int64_t g0, int j, int64_t k
 
 // One group of a row-major block: KG of the block's pieces (slots g0 .. g0+KG-1, interleaved
 // over the grid as in reduce_kernel_rows), all rows swept once, then the group epilogue.
-// PFG (cross-group prefetch): x arrives holding this group's first D steps (issued by the previous
-// group, or by the kernel for the first), and after this group's last row the first D steps of the
-// NEXT group (slot g0 + KG) are issued into x BEFORE this group's epilogue — so its result stores
-// are younger than those loads, and the next group's first wait (vmcnt counts loads and stores in
-// order) does not wait for them; without PFG every group end drained the stores before the next
-// group's first product (NS: the result stores cost ~2.3x their bytes, profiles/r04/nostore).
-template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB, bool TR, int XLM = -1,
-          bool PFG = false>
+// XL: whole-line f64 state / result stores (buf_store_tquad).
+// Dead ends, measured and removed (profiles/HISTORY.md §4): the next group's first loads issued
+// before this group's epilogue stores (finding 24); the last pieces' sums parked in LDS so that XL
+// fits KG = 4 (finding 23); a per-quad epilogue through finish_quad (finding 10).
+template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB, bool TR, bool XL>
 __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, int64_t row_bytes, int n,
                                                const typename P::w_t* __restrict__ w, int64_t g0, int64_t k,
                                                int64_t pc, int64_t pieces, int64_t nquads, int64_t ncols,
@@ -1325,10 +1130,8 @@ __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, in
     const __amdgpu_buffer_rsrc_t r_ = row_rsrc(base + qb[j] * 16 + (int64_t)(row) * row_bytes, bytes[j]); \
     _Pragma("unroll") for (int v = 0; v < V; ++v) x[slot][v] = buf_load_quad<NT>(r_, voff + v * 64 * W * 16, 0); \
   }
-  if constexpr (!PFG) {
 #pragma unroll
-    for (int d = 0; d < D; ++d) FA_RM_LOAD(d, 0, d);
-  }
+  for (int d = 0; d < D; ++d) FA_RM_LOAD(d, 0, d);
   // row 0: products initialise the sums
 #pragma unroll
   for (int j = 0; j < KG; ++j) {
@@ -1369,65 +1172,11 @@ __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, in
     }
   }
 #undef FA_RM_LOAD
-  if constexpr (PFG) {  // the next group's first D steps, before this group's epilogue stores
-    if (g0 + KG < k) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        int64_t qn;
-        uint32_t bn;
-        rowmajor_piece_geom(g0 + KG, d, k, pc, pieces, nquads, ncols, &qn, &bn);
-        const __amdgpu_buffer_rsrc_t r_ = row_rsrc(base + qn * 16, bn);
-#pragma unroll
-        for (int v = 0; v < V; ++v) x[d][v] = buf_load_quad<NT>(r_, voff + v * 64 * W * 16, 0);
-      }
-    }
-  }
   if constexpr (TR) {
     if (threadIdx.x == 0 && gi < 7) e.trace[blockIdx.x * 16 + 1 + 2 * gi] = wall_clock64();
   }
-  if constexpr (EPIB == 0) {  // per-quad epilogue (tuning reference: tools/tune_reduce.hip set "epib")
 #pragma unroll
-    for (int j = 0; j < KG; ++j) {
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const int q = v * 64 * W + (int)threadIdx.x;
-        const int valid = (int)(bytes[j] / 4) - q * 4;
-        if (valid > 0) finish_quad<T, OP, A>(e, (qb[j] + q) * 4, valid < 4 ? valid : 4, acc[j][v]);
-      }
-    }
-  } else {
-    // whole-line f64 state / result stores where they cost no spills: the fused ops at KG <= 3
-    // (at KG = 4 the LDS regrouping pushes the kernel past 256 + 256 registers; finding 22)
-    // (XLM: -1 this rule, 0 / 1 forced off / on by the tuner; 2: on, with the last KG/2 pieces'
-    // sums parked in LDS while the first ones finish, so the regrouping has registers to use)
-    constexpr bool XL = XLM >= 0 ? XLM >= 1 : (sizeof(T) == 8 && OP != FA_OP_MEAN && KG <= 3);
-    if constexpr (XLM == 2 && KG >= 2) {
-      constexpr int KP = KG / 2;  // pieces parked
-      // lane-private slots, [piece][slot][thread]: consecutive lanes, consecutive 16 B (no bank
-      // conflicts); a wave reads only what its own lanes wrote, in program order (no barrier)
-      __shared__ AV park[KP][V][64 * W];
-#pragma unroll
-      for (int j = 0; j < KP; ++j)
-#pragma unroll
-        for (int v = 0; v < V; ++v) park[j][v][threadIdx.x] = acc[KG - KP + j][v];
-      // the compiler must not forward the stored values (that would keep them in registers)
-      __atomic_signal_fence(__ATOMIC_SEQ_CST);
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int j = 0; j < KG - KP; ++j) finish_piece<T, OP, A, V, 64 * W, EPIB, XL>(e, qb[j], (int)(bytes[j] / 4), acc[j]);
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int j = 0; j < KP; ++j) {
-        AV a2[V];
-#pragma unroll
-        for (int v = 0; v < V; ++v) a2[v] = park[j][v][threadIdx.x];
-        finish_piece<T, OP, A, V, 64 * W, EPIB, XL>(e, qb[KG - KP + j], (int)(bytes[KG - KP + j] / 4), a2);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < KG; ++j) finish_piece<T, OP, A, V, 64 * W, EPIB, XL>(e, qb[j], (int)(bytes[j] / 4), acc[j]);
-    }
-  }
+  for (int j = 0; j < KG; ++j) finish_piece<T, OP, A, V, 64 * W, EPIB, XL>(e, qb[j], (int)(bytes[j] / 4), acc[j]);
   if constexpr (TR) {
     if (threadIdx.x == 0 && gi < 7) e.trace[blockIdx.x * 16 + 2 + 2 * gi] = wall_clock64();
   }
@@ -1443,8 +1192,11 @@ __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, in
 // 0..N-1 in order.
 // TR (tools/tune_reduce.hip set "timeline"): wave 0 of every block stamps the 100-MHz wall clock
 // at its start and at each group's sweep end and epilogue end into e.trace[block * 16 + slot].
+// EPIB: slots per lane whose state the piece epilogue loads at once (finish_piece's B).
+// XL: whole-line f64 state / result stores; by default where they cost no spills: the fused ops at
+// KG <= 3 (at KG = 4 the LDS regrouping pushes the kernel past 256 + 256 registers; finding 22).
 template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB = (V >= 2 ? 2 : V),
-          bool TR = false, int XLM = -1, bool PFG = false>
+          bool TR = false, bool XL = (sizeof(T) == 8 && OP != FA_OP_MEAN && KG <= 3)>
 __global__ __launch_bounds__(64 * W) void reduce_kernel_rowmajor(const float* __restrict__ stack,
                                                                  int64_t stride, int n,
                                                                  const typename P::w_t* __restrict__ w,
@@ -1461,49 +1213,12 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_rowmajor(const float* __
   if constexpr (TR) {
     if (threadIdx.x == 0) e.trace[blockIdx.x * 16] = wall_clock64();
   }
-  typename vec4<float>::type x[D][V];
-  if constexpr (PFG) {  // the first group's first D steps (later groups get theirs from the previous one)
-    const int voff = (int)threadIdx.x * 16;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      int64_t q0;
-      uint32_t b0;
-      rowmajor_piece_geom(0, d, k, pc, pieces, nquads, ncols, &q0, &b0);
-      const __amdgpu_buffer_rsrc_t r_ = row_rsrc(base + q0 * 16, b0);
-#pragma unroll
-      for (int v = 0; v < V; ++v) x[d][v] = buf_load_quad<NT>(r_, voff + v * 64 * W * 16, 0);
-    }
-  }
-#define FA_RM_GROUP(KGX, G0, GI) \
-  rowmajor_group<P, T, OP, V, D, W, KGX, NT, EPIB, TR, XLM, PFG>(base, row_bytes, n, w, G0, k, pc, pieces, nquads, ncols, \
-                                                                 GI, e, x)
+  static_assert(EPIB >= 1, "the piece epilogue batches at least one slot");
+  typename vec4<float>::type x[D][V];  // the pipeline's slots
   int gi = 0;
-  for (int64_t g0 = 0; g0 < k; g0 += KG) FA_RM_GROUP(KG, g0, gi++);
-#undef FA_RM_GROUP
-}
-
-// Column-blocked client stack: element (n, c) lives at ((c / B) * N + n) * B + c % B with
-// B = kThreads*V*4 columns (one tile).  Tile b's N rows are one contiguous N*B*4-byte region, so
-// a block streams its whole tile linearly (rows B*4 bytes apart) — the access pattern of a plain
-// streaming read.  One tile per block; the window is the whole (padded) bucket.
-template <class P, typename T, int OP, int V, int U, bool NT>
-__global__ __launch_bounds__(kThreads) void reduce_kernel_blocked(
-    const typename P::x_t* __restrict__ stack, int n, const typename P::w_t* __restrict__ w,
-    int64_t ncols, Epi<T> e) {
-  constexpr int64_t B = (int64_t)kThreads * V * 4;
-  const int64_t tile = blockIdx.x;
-  const typename P::x_t* base = stack + tile * (int64_t)n * B;
-  Epi<T> et = e;
-  if (et.out32) et.out32 += tile * B;
-  if (et.out64) et.out64 += tile * B;
-  if constexpr (OP != FA_OP_MEAN) {
-    if (et.prev) et.prev += tile * B;
-    if (et.h) et.h += tile * B;
-    et.v += tile * B;
-  }
-  const int64_t cols = ncols - tile * B < B ? ncols - tile * B : B;
-  reduce_range_subtile<P, T, OP, V, U, NT, (sizeof(typename P::x_t) == 4)>(
-      base, B, n, w, 0, (cols + 3) / 4, cols, et);
+  for (int64_t g0 = 0; g0 < k; g0 += KG)
+    rowmajor_group<P, T, OP, V, D, W, KG, NT, EPIB, TR, XL>(base, row_bytes, n, w, g0, k, pc, pieces, nquads, ncols,
+                                                            gi++, e, x);
 }
 
 // Standalone update (client_receive form): g read from memory instead of reduced.

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <atomic>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fa_device.hpp"
@@ -31,6 +32,20 @@ thread_local std::string g_last_error;
 int fail(int code, const char* what) {
   g_last_error = what;
   return code;
+}
+
+// The runtime epilogue op as a compile-time constant: f(std::integral_constant<int, OP>{}).
+template <class F>
+int with_op(int op, F&& f) {
+  switch (op) {
+    case FA_OP_MEAN: return f(std::integral_constant<int, FA_OP_MEAN>{});
+    case FA_OP_AVGM: return f(std::integral_constant<int, FA_OP_AVGM>{});
+    case FA_OP_ADAGRAD: return f(std::integral_constant<int, FA_OP_ADAGRAD>{});
+    case FA_OP_YOGI: return f(std::integral_constant<int, FA_OP_YOGI>{});
+    case FA_OP_ADAM: return f(std::integral_constant<int, FA_OP_ADAM>{});
+    case FA_OP_DYN: return f(std::integral_constant<int, FA_OP_DYN>{});
+    default: return fail(FA_ERR_ARG, "unknown epilogue op");
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -140,6 +155,16 @@ int launch_rowmajor(const float* stack, int64_t stride, int n, const typename P:
   return launch_check();
 }
 
+template <class P, typename T, int OP>
+int launch_rowmajor_kg(int kg, const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
+                       int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
+  switch (kg) {
+    case 2: return launch_rowmajor<P, T, OP, 2>(stack, stride, n, w, col0, ncols, e, grid, s);
+    case 3: return launch_rowmajor<P, T, OP, 3>(stack, stride, n, w, col0, ncols, e, grid, s);
+    default: return launch_rowmajor<P, T, OP, 4>(stack, stride, n, w, col0, ncols, e, grid, s);
+  }
+}
+
 // Row-major geometry for windows of several 64-KiB pieces per block (k >= 2): a grid near 192
 // blocks whose k splits into equal groups of KG in {4, 3, 2} pieces (every step of a group is
 // a real piece).  Returns false when no grid in [160, cus] gives such a k.
@@ -198,11 +223,7 @@ int launch_reduce_window(const typename P::x_t* stack, int64_t stride, int n, co
       if (forced > 0 && chunks > (int64_t)forced * kPieceChunks) {
         g = forced;
         kg = kg_for((chunks + g * kPieceChunks - 1) / (g * kPieceChunks));
-        switch (kg) {
-          case 2: return launch_rowmajor<P, T, OP, 2>(stack, stride, n, wt, col0, ncols, e, g, s);
-          case 3: return launch_rowmajor<P, T, OP, 3>(stack, stride, n, wt, col0, ncols, e, g, s);
-          default: return launch_rowmajor<P, T, OP, 4>(stack, stride, n, wt, col0, ncols, e, g, s);
-        }
+        return launch_rowmajor_kg<P, T, OP>(kg, stack, stride, n, wt, col0, ncols, e, g, s);
       }
       // Past one round of the grid: row-major groups.  So also where one piece per block would
       // take more than rows_grid_max blocks — two pieces per block on a grid near 13/16 of the
@@ -212,11 +233,7 @@ int launch_reduce_window(const typename P::x_t* stack, int64_t stride, int n, co
       if (forced <= 0 && chunks > rows_grid_max(cus) * kPieceChunks &&
           rowmajor_geometry(chunks, cus, past ? (int64_t)(cus * kRowsBlocksPerCU + 0.5) : (int64_t)cus * 13 / 16, &g,
                             &kg)) {
-        switch (kg) {
-          case 2: return launch_rowmajor<P, T, OP, 2>(stack, stride, n, wt, col0, ncols, e, g, s);
-          case 3: return launch_rowmajor<P, T, OP, 3>(stack, stride, n, wt, col0, ncols, e, g, s);
-          default: return launch_rowmajor<P, T, OP, 4>(stack, stride, n, wt, col0, ncols, e, g, s);
-        }
+        return launch_rowmajor_kg<P, T, OP>(kg, stack, stride, n, wt, col0, ncols, e, g, s);
       }
     }
     int64_t grid = forced > 0 ? forced : (int64_t)(cus * kRowsBlocksPerCU + 0.5);
@@ -330,7 +347,7 @@ Epi<T> epi_at(const Epi<T>& e, int64_t c) {  // the epilogue's per-column arrays
   return o;
 }
 
-template <class P, typename T, int OP>
+template <class P, int OP, typename T>
 int launch_reduce(const typename P::x_t* stack, int64_t stride, int n, const void* w, int64_t col0,
                   int64_t ncols, const Epi<T>& e, hipStream_t s) {
   int S = 1;
@@ -357,7 +374,7 @@ constexpr double kSegBlocksPerCU = 0.75;
 constexpr int kSegW = 8, kSegV = 8, kSegKG = 2;                // row-major groups of 2 pieces, 8 x 8 KiB
 constexpr int64_t kSegWideCols = (int64_t)64 * kSegW * 4;      // wider pieces go into groups
 
-template <class P, typename T, int OP>
+template <class P, int OP, typename T>
 int launch_segrows(const float* const* rows, int n, const void* w, const fa_piece* pieces, int64_t npieces,
                    int grid, int32_t* work, const Epi<T>& e, hipStream_t s) {
   const typename P::w_t* wt = static_cast<const typename P::w_t*>(w);
@@ -366,23 +383,9 @@ int launch_segrows(const float* const* rows, int n, const void* w, const fa_piec
   // fused f64 state: whole-line stores (FedAVGM 100 x ResNet-50 uploads in place 1647.6 -> 1633.8 us,
   // bit-identical: tools/probe_rows_xl.py, profiles/r05/rows_xl/)
   constexpr bool XLS = sizeof(T) == 8 && OP != FA_OP_MEAN;
-  hipLaunchKernelGGL((reduce_kernel_segrows_rm<P, T, OP, kSegV, kSegW, KG, 16, kNT, false, 1, false, 0, 0, XLS>),
+  hipLaunchKernelGGL((reduce_kernel_segrows_rm<P, T, OP, kSegV, kSegW, KG, 16, kNT, false, XLS>),
                      dim3((unsigned)grid), dim3(64 * kSegW), 0, s, rows, n, wt, pieces, npieces, work, e);
   return launch_check();
-}
-
-template <class P, typename T>
-int dispatch_segrows(int op, const float* const* rows, int n, const void* w, const fa_piece* pieces,
-                     int64_t npieces, int grid, int32_t* work, const Epi<T>& e, hipStream_t s) {
-  switch (op) {
-    case FA_OP_MEAN: return launch_segrows<P, T, FA_OP_MEAN>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case FA_OP_AVGM: return launch_segrows<P, T, FA_OP_AVGM>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case FA_OP_ADAGRAD: return launch_segrows<P, T, FA_OP_ADAGRAD>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case FA_OP_YOGI: return launch_segrows<P, T, FA_OP_YOGI>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case FA_OP_ADAM: return launch_segrows<P, T, FA_OP_ADAM>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case FA_OP_DYN: return launch_segrows<P, T, FA_OP_DYN>(rows, n, w, pieces, npieces, grid, work, e, s);
-    default: return fail(FA_ERR_ARG, "unknown epilogue op");
-  }
 }
 
 // Split-N geometry (tools/tune_splitn.py, profiles/r02/tune_splitn): one 1-KiB chunk of every row
@@ -399,44 +402,15 @@ int dispatch_segrows(int op, const float* const* rows, int n, const void* w, con
 constexpr int kSplitW = 4, kSplitD = 8, kSplitMaxN = 256;
 constexpr int kSplitS = kSplitW;
 
-template <class P, typename T, int OP>
+template <class P, int OP, typename T>
 int launch_splitn(const float* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
                   const Epi<T>& e, hipStream_t s) {
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
   if (n < 2 * kSplitS || n > kSplitMaxN || chunks >= device_cus())  // see kSplitMaxN
-    return launch_reduce<P, T, OP>(stack, stride, n, w, col0, ncols, e, s);
+    return launch_reduce<P, OP>(stack, stride, n, w, col0, ncols, e, s);
   hipLaunchKernelGGL((reduce_kernel_splitn<P, T, OP, kSplitW, kSplitD, kNT>), dim3((unsigned)chunks),
                      dim3(64 * kSplitW), 0, s, stack, stride, n, static_cast<const typename P::w_t*>(w), col0, ncols, e);
   return launch_check();
-}
-
-template <class P, typename T>
-int dispatch_splitn(int op, const float* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
-                    const Epi<T>& e, hipStream_t s) {
-  switch (op) {
-    case FA_OP_MEAN: return launch_splitn<P, T, FA_OP_MEAN>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_AVGM: return launch_splitn<P, T, FA_OP_AVGM>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_ADAGRAD: return launch_splitn<P, T, FA_OP_ADAGRAD>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_YOGI: return launch_splitn<P, T, FA_OP_YOGI>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_ADAM: return launch_splitn<P, T, FA_OP_ADAM>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_DYN: return launch_splitn<P, T, FA_OP_DYN>(stack, stride, n, w, col0, ncols, e, s);
-    default: return fail(FA_ERR_ARG, "unknown epilogue op");
-  }
-}
-
-template <class P, typename T>
-int dispatch_op(int op, const typename P::x_t* stack, int64_t stride, int n, const void* w,
-                int64_t col0, int64_t ncols, const Epi<T>& e, hipStream_t s) {
-  switch (op) {
-    case FA_OP_MEAN: return launch_reduce<P, T, FA_OP_MEAN>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_AVGM: return launch_reduce<P, T, FA_OP_AVGM>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_ADAGRAD:
-      return launch_reduce<P, T, FA_OP_ADAGRAD>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_YOGI: return launch_reduce<P, T, FA_OP_YOGI>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_ADAM: return launch_reduce<P, T, FA_OP_ADAM>(stack, stride, n, w, col0, ncols, e, s);
-    case FA_OP_DYN: return launch_reduce<P, T, FA_OP_DYN>(stack, stride, n, w, col0, ncols, e, s);
-    default: return fail(FA_ERR_ARG, "unknown epilogue op");
-  }
 }
 
 bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
@@ -491,6 +465,23 @@ int make_epi(const fa_epilogue* in, double denom, int n_reduced, float* out32, d
   return FA_OK;
 }
 
+// The fp32 reduce mode as its accumulation policy P and epilogue precision T: builds the Epi<T>
+// (make_epi; ncols as there) and calls f(P{}, e).
+template <class F>
+int with_mode(int mode, const fa_epilogue* epi, double denom, int n_clients, float* out32, double* out64,
+              int64_t ncols, F&& f) {
+  auto go = [&](auto p, auto t) {
+    Epi<decltype(t)> e;
+    if (int rc = make_epi(epi, denom, n_clients, out32, out64, &e, ncols)) return rc;
+    return f(p, e);
+  };
+  switch (mode) {
+    case FA_MODE_W32_DIV64: return go(AccF32{}, double{});
+    case FA_MODE_W32_DIV32: return go(AccF32{}, float{});
+    case FA_MODE_W64: return go(AccF32W64{}, double{});
+    default: return fail(FA_ERR_ARG, "unknown reduce mode");
+  }
+}
 
 // per-column arrays are accessed with 4-element vector loads/stores
 int check_columns(const float* out32, const double* out64, const void* prev, const void* v,
@@ -544,25 +535,11 @@ int fa_reduce_f32(const float* stack, int64_t row_stride, int32_t n_clients, int
                           epi ? epi->h : nullptr)))
     return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == FA_MODE_W32_DIV64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(epi, denom, n_clients, out32, out64, &e, n_cols))) return rc;
-    return dispatch_op<AccF32, double>(op, stack, row_stride, n_clients, weights, col_begin, n_cols,
-                                       e, s);
-  }
-  if (mode == FA_MODE_W32_DIV32) {
-    Epi<float> e;
-    if ((rc = make_epi<float>(epi, denom, n_clients, out32, out64, &e, n_cols))) return rc;
-    return dispatch_op<AccF32, float>(op, stack, row_stride, n_clients, weights, col_begin, n_cols,
-                                      e, s);
-  }
-  if (mode == FA_MODE_W64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(epi, denom, n_clients, out32, out64, &e, n_cols))) return rc;
-    return dispatch_op<AccF32W64, double>(op, stack, row_stride, n_clients, weights, col_begin,
-                                          n_cols, e, s);
-  }
-  return fail(FA_ERR_ARG, "unknown reduce mode");
+  return with_mode(mode, epi, denom, n_clients, out32, out64, n_cols, [&](auto p, const auto& e) {
+    return with_op(op, [&](auto OP) {
+      return launch_reduce<decltype(p), OP()>(stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+    });
+  });
 }
 
 int fa_reduce_f32_splitn(const float* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
@@ -576,22 +553,11 @@ int fa_reduce_f32_splitn(const float* stack, int64_t row_stride, int32_t n_clien
                           mode == FA_MODE_W32_DIV32 ? sizeof(float) : sizeof(double), epi ? epi->h : nullptr)))
     return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == FA_MODE_W32_DIV64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(epi, denom, n_clients, out32, out64, &e, n_cols))) return rc;
-    return dispatch_splitn<AccF32, double>(op, stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
-  }
-  if (mode == FA_MODE_W32_DIV32) {
-    Epi<float> e;
-    if ((rc = make_epi<float>(epi, denom, n_clients, out32, out64, &e, n_cols))) return rc;
-    return dispatch_splitn<AccF32, float>(op, stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
-  }
-  if (mode == FA_MODE_W64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(epi, denom, n_clients, out32, out64, &e, n_cols))) return rc;
-    return dispatch_splitn<AccF32W64, double>(op, stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
-  }
-  return fail(FA_ERR_ARG, "unknown reduce mode");
+  return with_mode(mode, epi, denom, n_clients, out32, out64, n_cols, [&](auto p, const auto& e) {
+    return with_op(op, [&](auto OP) {
+      return launch_splitn<decltype(p), OP()>(stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+    });
+  });
 }
 
 int fa_reduce_f64(const double* stack, int64_t row_stride, int32_t n_clients,
@@ -603,7 +569,7 @@ int fa_reduce_f64(const double* stack, int64_t row_stride, int32_t n_clients,
   if ((rc = check_columns(nullptr, out64, nullptr, nullptr, 8))) return rc;
   Epi<double> e;
   make_epi<double>(nullptr, denom, n_clients, nullptr, out64, &e);
-  return launch_reduce<AccF64, double, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
+  return launch_reduce<AccF64, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
                                                    n_cols, e, static_cast<hipStream_t>(stream));
 }
 
@@ -616,7 +582,7 @@ int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
   if ((rc = check_columns(nullptr, out64, nullptr, nullptr, 8))) return rc;
   Epi<double> e;
   make_epi<double>(nullptr, denom, n_clients, nullptr, out64, &e);
-  return launch_reduce<AccI64, double, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
+  return launch_reduce<AccI64, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
                                                    n_cols, e, static_cast<hipStream_t>(stream));
 }
 
@@ -637,37 +603,22 @@ int fa_opt_apply(int32_t prec, const fa_epilogue* epi, const float* local, const
   if (epi->op != FA_OP_DYN) local_epi.prev = local;
   const int64_t blocks = (n + kThreads * 4 - 1) / (kThreads * 4);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int rc;
-#define FA_APPLY(T, OPV)                                                                   \
-  hipLaunchKernelGGL((apply_kernel<T, OPV>), dim3((unsigned)blocks), dim3(kThreads), 0, s, \
-                     static_cast<const T*>(glob), n, e)
-  if (prec == FA_PREC_F64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(&local_epi, 1.0, 1, out32, out64, &e, n))) return rc;
-    switch (epi->op) {
-      case FA_OP_AVGM: FA_APPLY(double, FA_OP_AVGM); break;
-      case FA_OP_ADAGRAD: FA_APPLY(double, FA_OP_ADAGRAD); break;
-      case FA_OP_YOGI: FA_APPLY(double, FA_OP_YOGI); break;
-      case FA_OP_DYN: FA_APPLY(double, FA_OP_DYN); break;
-      default: FA_APPLY(double, FA_OP_ADAM); break;
-    }
-  } else if (prec == FA_PREC_F32) {
-    Epi<float> e;
-    if ((rc = make_epi<float>(&local_epi, 1.0, 1, out32, out64, &e, n))) return rc;
-    switch (epi->op) {
-      case FA_OP_AVGM: FA_APPLY(float, FA_OP_AVGM); break;
-      case FA_OP_ADAGRAD: FA_APPLY(float, FA_OP_ADAGRAD); break;
-      case FA_OP_YOGI: FA_APPLY(float, FA_OP_YOGI); break;
-      case FA_OP_DYN: FA_APPLY(float, FA_OP_DYN); break;
-      default: FA_APPLY(float, FA_OP_ADAM); break;
-    }
-  } else {
-    return fail(FA_ERR_ARG, "unknown precision");
-  }
-#undef FA_APPLY
-  return launch_check();
+  // make_epi has rejected every op but the optimizers' by the time the kernel is chosen
+  auto apply = [&](auto t) {
+    typedef decltype(t) T;
+    Epi<T> e;
+    if (int rc = make_epi(&local_epi, 1.0, 1, out32, out64, &e, n)) return rc;
+    return with_op(epi->op, [&](auto OP) {
+      if constexpr (OP() != FA_OP_MEAN)
+        hipLaunchKernelGGL((apply_kernel<T, OP()>), dim3((unsigned)blocks), dim3(kThreads), 0, s,
+                           static_cast<const T*>(glob), n, e);
+      return launch_check();
+    });
+  };
+  if (prec == FA_PREC_F64) return apply(double{});
+  if (prec == FA_PREC_F32) return apply(float{});
+  return fail(FA_ERR_ARG, "unknown precision");
 }
-
 
 int fa_rows_plan(int32_t n_segments, const int64_t* seg_col, const int64_t* seg_len, int32_t op,
                  int32_t grid_hint, fa_piece* pieces, int64_t cap, int64_t* n_pieces, int32_t* grid) {
@@ -751,22 +702,12 @@ int fa_reduce_f32_rows(const float* const* rows, int32_t n_clients, int32_t mode
     return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(work, 0, sizeof(int32_t), s) != hipSuccess) return fail(FA_ERR_LAUNCH, "clearing the piece counter");
-  if (mode == FA_MODE_W32_DIV64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(epi, denom, n_clients, out32, out64, &e))) return rc;
-    return dispatch_segrows<AccF32, double>(op, rows, n_clients, weights, pieces, n_pieces, grid, work, e, s);
-  }
-  if (mode == FA_MODE_W32_DIV32) {
-    Epi<float> e;
-    if ((rc = make_epi<float>(epi, denom, n_clients, out32, out64, &e))) return rc;
-    return dispatch_segrows<AccF32, float>(op, rows, n_clients, weights, pieces, n_pieces, grid, work, e, s);
-  }
-  if (mode == FA_MODE_W64) {
-    Epi<double> e;
-    if ((rc = make_epi<double>(epi, denom, n_clients, out32, out64, &e))) return rc;
-    return dispatch_segrows<AccF32W64, double>(op, rows, n_clients, weights, pieces, n_pieces, grid, work, e, s);
-  }
-  return fail(FA_ERR_ARG, "unknown reduce mode");
+  // (no column count for make_epi: the pieces, not one window, say which columns are touched)
+  return with_mode(mode, epi, denom, n_clients, out32, out64, 0, [&](auto p, const auto& e) {
+    return with_op(op, [&](auto OP) {
+      return launch_segrows<decltype(p), OP()>(rows, n_clients, weights, pieces, n_pieces, grid, work, e, s);
+    });
+  });
 }
 
 int fa_gather_rows(void* stack, int64_t row_stride, int32_t n_clients, int32_t elem_size,
@@ -807,12 +748,7 @@ int fa_gather_rows_f64(double* stack, int64_t row_stride, int32_t n_clients, con
 int fa_reduce_windows(int32_t op, int64_t n_cols) {
   if (n_cols < 0) return fail(FA_ERR_ARG, "negative n_cols");
   if (g_reduce_grid.load(std::memory_order_relaxed) > 0) return 1;
-  switch (op) {
-    case FA_OP_MEAN: return window_count<FA_OP_MEAN>(n_cols);
-    case FA_OP_AVGM: case FA_OP_ADAGRAD: case FA_OP_YOGI: case FA_OP_ADAM: case FA_OP_DYN:
-      return window_count<FA_OP_AVGM>(n_cols);
-    default: return fail(FA_ERR_ARG, "unknown epilogue op");
-  }
+  return with_op(op, [&](auto OP) { return window_count<OP()>(n_cols); });
 }
 
 int fa_set_reduce_grid(int32_t grid) {

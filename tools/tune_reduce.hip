@@ -1,6 +1,6 @@
 // tune_reduce.hip — geometry sweep of the fused reduce kernel on the MI355X.
 //
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -Iflearn_amd/csrc \
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude \
 //         tools/tune_reduce.hip -o tools/tune_reduce
 //   tools/tune_reduce [n_clients=100] [n_cols=11699136] [rounds=7] [op=mean|avgm]
 //
@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "fa_device.hpp"
+#include "fa_tune_device.hpp"
 
 #define CK(x)                                                                        \
   do {                                                                               \
@@ -426,7 +426,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_rowmajor_tail(const floa
     int gi = 0;
     typename vec4<float>::type x[D][V];
     for (int64_t g0 = 0; g0 < k; g0 += KG)
-      rowmajor_group<P, T, OP, V, D, W, KG, NT, EPIB, false>(base, row_bytes, n, w, g0, k, pc, pieces, nquads_s,
+      rowmajor_group<P, T, OP, V, D, W, KG, NT, EPIB, false, (sizeof(T) == 8 && OP != FA_OP_MEAN && KG <= 3)>(base, row_bytes, n, w, g0, k, pc, pieces, nquads_s,
                                                             ncols_static, gi++, e, x);
   }
   // the tail: strips of 64*W quads from quad ncols_static/4 (ncols_static is a multiple of 4)
@@ -609,9 +609,9 @@ Variant make_oneshot(const float* stack, int64_t stride, int n, const float* w, 
 template <int V, int U, bool NT, int OP, typename T, bool BUF = false>
 Variant make_balanced(const float* stack, int64_t stride, int n, const float* w, int64_t ncols,
                       Epi<T> e, double bytes, int cus, int rounds_extra) {
+  auto kern = BUF ? reduce_kernel_balanced_buf<AccF32, T, OP, V, U, NT> : reduce_kernel_balanced<AccF32, T, OP, V, U, NT>;
   int occ = 0;
-  CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reduce_kernel_balanced<AccF32, T, OP, V, U, NT, BUF>,
-                                                  256, 0));
+  CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0));
   const int64_t slots = (int64_t)cus * occ;
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
   const int64_t k = (chunks + slots * 4 * V - 1) / (slots * 4 * V) + rounds_extra;
@@ -620,24 +620,22 @@ Variant make_balanced(const float* stack, int64_t stride, int n, const float* w,
   snprintf(name, sizeof name, "balanced%s V%d U%d occ%d g%d", BUF ? "-buf" : "", V, U, occ, grid);
   return {name, bytes,
           [=] {
-            hipLaunchKernelGGL((reduce_kernel_balanced<AccF32, T, OP, V, U, NT, BUF>), dim3(grid), dim3(256), 0, 0,
-                               stack, stride, n, w, (int64_t)0, ncols, e);
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
           },
           true, {}};
 }
 
-template <int V, int D, int W, int OP, typename T, bool IL = true, bool XM = false, bool NTL = true>
+template <int V, int D, int W, int OP, typename T, bool NTL = true>
 Variant make_rows(const float* stack, int64_t stride, int n, const float* w, int64_t ncols, Epi<T> e,
                   double bytes, int64_t max_grid = 0) {
   int64_t grid = ((ncols + 3) / 4 + 64 * W * V - 1) / (64 * W * V);
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
   if (max_grid > 0) grid = max_grid < chunks ? max_grid : chunks;
   char name[96];
-  snprintf(name, sizeof name, "rows%s%s%s V%d D%d W%d g%lld", IL ? "-il" : "-ct", XM ? "-xcd" : "",
-           NTL ? "" : "-temporal", V, D, W, (long long)grid);
+  snprintf(name, sizeof name, "rows-il%s V%d D%d W%d g%lld", NTL ? "" : "-temporal", V, D, W, (long long)grid);
   return {name, bytes,
           [=] {
-            hipLaunchKernelGGL((reduce_kernel_rows<AccF32, T, OP, V, D, W, NTL, IL, XM>), dim3((unsigned)grid),
+            hipLaunchKernelGGL((reduce_kernel_rows<AccF32, T, OP, V, D, W, NTL>), dim3((unsigned)grid),
                                dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
           },
           true, {}};
@@ -673,32 +671,16 @@ Variant make_narrow_lb(const float* stack, int64_t stride, int n, const float* w
           true, {}};
 }
 
-template <int V, int D, int W, int KG, int OP, typename T, int EPIB, int XLM>
+template <int V, int D, int W, int KG, int OP, typename T, int EPIB, bool XL>
 Variant make_rowmajor_xl(const float* stack, int64_t stride, int n, const float* w, int64_t ncols, Epi<T> e,
                          double bytes, int64_t grid) {
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
   if (grid > chunks) grid = chunks;
   char name[96];
-  snprintf(name, sizeof name, "rowmajor V%d W%d KG%d g%lld epib%d xl%d", V, W, KG, (long long)grid, EPIB, XLM);
+  snprintf(name, sizeof name, "rowmajor V%d W%d KG%d g%lld epib%d xl%d", V, W, KG, (long long)grid, EPIB, (int)XL);
   return {name, bytes,
           [=] {
-            hipLaunchKernelGGL((reduce_kernel_rowmajor<AccF32, T, OP, V, D, W, KG, true, EPIB, false, XLM>),
-                               dim3((unsigned)grid), dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
-          },
-          true, {}};
-}
-
-template <int V, int D, int W, int KG, int OP, typename T, int EPIB, int XLM, bool PFG>
-Variant make_rowmajor_pfg(const float* stack, int64_t stride, int n, const float* w, int64_t ncols, Epi<T> e,
-                          double bytes, int64_t grid) {
-  const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
-  if (grid > chunks) grid = chunks;
-  char name[112];
-  snprintf(name, sizeof name, "rowmajor V%d W%d KG%d g%lld epib%d xl%d pfg%d", V, W, KG, (long long)grid, EPIB, XLM,
-           (int)PFG);
-  return {name, bytes,
-          [=] {
-            hipLaunchKernelGGL((reduce_kernel_rowmajor<AccF32, T, OP, V, D, W, KG, true, EPIB, false, XLM, PFG>),
+            hipLaunchKernelGGL((reduce_kernel_rowmajor<AccF32, T, OP, V, D, W, KG, true, EPIB, false, XL>),
                                dim3((unsigned)grid), dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
           },
           true, {}};
@@ -993,14 +975,10 @@ int main(int argc, char** argv) {
                : op == FA_OP_ADAGRAD ? make_rows<V, D, W, FA_OP_ADAGRAD, double>(stack, stride, n, w, ncols, e, bytes, G) \
                                      : make_rows<V, D, W, FA_OP_MEAN, double>(stack, stride, n, w, ncols, e, bytes, G))
 #define ROWS(V, D, W) ROWSG(V, D, W, 0)
-#define ROWSC(V, D, W, G)                                                                                      \
-  vs.push_back(op == FA_OP_AVGM      ? make_rows<V, D, W, FA_OP_AVGM, double, false>(stack, stride, n, w, ncols, e, bytes, G)   \
-               : op == FA_OP_ADAGRAD ? make_rows<V, D, W, FA_OP_ADAGRAD, double, false>(stack, stride, n, w, ncols, e, bytes, G) \
-                                     : make_rows<V, D, W, FA_OP_MEAN, double, false>(stack, stride, n, w, ncols, e, bytes, G))
-#define ROWSX(V, D, W, G, XM, NTL)                                                                                      \
-  vs.push_back(op == FA_OP_AVGM      ? make_rows<V, D, W, FA_OP_AVGM, double, true, XM, NTL>(stack, stride, n, w, ncols, e, bytes, G)   \
-               : op == FA_OP_ADAGRAD ? make_rows<V, D, W, FA_OP_ADAGRAD, double, true, XM, NTL>(stack, stride, n, w, ncols, e, bytes, G) \
-                                     : make_rows<V, D, W, FA_OP_MEAN, double, true, XM, NTL>(stack, stride, n, w, ncols, e, bytes, G))
+#define ROWSX(V, D, W, G, NTL)                                                                                      \
+  vs.push_back(op == FA_OP_AVGM      ? make_rows<V, D, W, FA_OP_AVGM, double, NTL>(stack, stride, n, w, ncols, e, bytes, G)   \
+               : op == FA_OP_ADAGRAD ? make_rows<V, D, W, FA_OP_ADAGRAD, double, NTL>(stack, stride, n, w, ncols, e, bytes, G) \
+                                     : make_rows<V, D, W, FA_OP_MEAN, double, NTL>(stack, stride, n, w, ncols, e, bytes, G))
 #define RM(V, D, W, KG, G)                                                                                      \
   vs.push_back(op == FA_OP_AVGM      ? make_rowmajor<V, D, W, KG, FA_OP_AVGM, double>(stack, stride, n, w, ncols, e, bytes, G)   \
                : op == FA_OP_ADAGRAD ? make_rowmajor<V, D, W, KG, FA_OP_ADAGRAD, double>(stack, stride, n, w, ncols, e, bytes, G) \
@@ -1030,14 +1008,14 @@ int main(int argc, char** argv) {
   vs.push_back(op == FA_OP_AVGM      ? make_narrow_lb<LB, D, FA_OP_AVGM, double>(stack, stride, n, w, ncols, e, bytes)   \
                : op == FA_OP_ADAGRAD ? make_narrow_lb<LB, D, FA_OP_ADAGRAD, double>(stack, stride, n, w, ncols, e, bytes) \
                                      : make_narrow_lb<LB, D, FA_OP_MEAN, double>(stack, stride, n, w, ncols, e, bytes))
-#define RMXL(KG, EB, XLM)                                                                                      \
-  vs.push_back(op == FA_OP_AVGM      ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_AVGM, double, EB, XLM>(stack, stride, n, w, ncols, e, bytes, 192)   \
-               : op == FA_OP_ADAGRAD ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_ADAGRAD, double, EB, XLM>(stack, stride, n, w, ncols, e, bytes, 192) \
-                                     : make_rowmajor_xl<16, 1, 4, KG, FA_OP_MEAN, double, EB, XLM>(stack, stride, n, w, ncols, e, bytes, 192))
-#define RMXLG(KG, EB, XLM, G)                                                                                      \
-  vs.push_back(op == FA_OP_AVGM      ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_AVGM, double, EB, XLM>(stack, stride, n, w, ncols, e, bytes, G)   \
-               : op == FA_OP_ADAGRAD ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_ADAGRAD, double, EB, XLM>(stack, stride, n, w, ncols, e, bytes, G) \
-                                     : make_rowmajor_xl<16, 1, 4, KG, FA_OP_MEAN, double, EB, XLM>(stack, stride, n, w, ncols, e, bytes, G))
+#define RMXL(KG, EB, XL)                                                                                      \
+  vs.push_back(op == FA_OP_AVGM      ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_AVGM, double, EB, XL>(stack, stride, n, w, ncols, e, bytes, 192)   \
+               : op == FA_OP_ADAGRAD ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_ADAGRAD, double, EB, XL>(stack, stride, n, w, ncols, e, bytes, 192) \
+                                     : make_rowmajor_xl<16, 1, 4, KG, FA_OP_MEAN, double, EB, XL>(stack, stride, n, w, ncols, e, bytes, 192))
+#define RMXLG(KG, EB, XL, G)                                                                                      \
+  vs.push_back(op == FA_OP_AVGM      ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_AVGM, double, EB, XL>(stack, stride, n, w, ncols, e, bytes, G)   \
+               : op == FA_OP_ADAGRAD ? make_rowmajor_xl<16, 1, 4, KG, FA_OP_ADAGRAD, double, EB, XL>(stack, stride, n, w, ncols, e, bytes, G) \
+                                     : make_rowmajor_xl<16, 1, 4, KG, FA_OP_MEAN, double, EB, XL>(stack, stride, n, w, ncols, e, bytes, G))
   if (!strcmp(set, "xlg")) {  // KG = 4 shapes: the product (KG 4, no XL) vs KG 3 with XL on a grid whose k splits in 3s
     const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
     int64_t g3 = 192;
@@ -1047,53 +1025,35 @@ int main(int argc, char** argv) {
     }
     printf("# KG 3 grid %lld\n", (long long)g3);
     for (int rep = 0; rep < 2; ++rep) {
-      RMXL(4, 4, 0);
-      if (g3 == 192) { RMXLG(3, 4, 1, 192); RMXLG(3, 4, 0, 192); }
-      else if (g3 == 196) { RMXLG(3, 4, 1, 196); RMXLG(3, 4, 0, 196); }
-      else if (g3 == 200) { RMXLG(3, 4, 1, 200); RMXLG(3, 4, 0, 200); }
-      else if (g3 == 204) { RMXLG(3, 4, 1, 204); RMXLG(3, 4, 0, 204); }
-      else { RMXLG(3, 4, 1, 208); RMXLG(3, 4, 0, 208); }
+      RMXL(4, 4, false);
+      if (g3 == 192) { RMXLG(3, 4, true, 192); RMXLG(3, 4, false, 192); }
+      else if (g3 == 196) { RMXLG(3, 4, true, 196); RMXLG(3, 4, false, 196); }
+      else if (g3 == 200) { RMXLG(3, 4, true, 200); RMXLG(3, 4, false, 200); }
+      else if (g3 == 204) { RMXLG(3, 4, true, 204); RMXLG(3, 4, false, 204); }
+      else { RMXLG(3, 4, true, 208); RMXLG(3, 4, false, 208); }
     }
   }
   if (!strcmp(set, "xl")) {  // whole-line f64 stores (LDS regrouping) off / on, the product geometry, each twice
     const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
     const int64_t k = (chunks + 192 * 64 - 1) / (192 * 64);
     if (k % 3 == 0) {
-      RMXL(3, 4, 0);
-      RMXL(3, 4, 1);
-      RMXL(3, 4, 0);
-      RMXL(3, 4, 1);
+      RMXL(3, 4, false);
+      RMXL(3, 4, true);
+      RMXL(3, 4, false);
+      RMXL(3, 4, true);
     } else {
-      RMXL(4, 4, 0);
-      RMXL(4, 4, 1);
-      RMXL(4, 4, 0);
-      RMXL(4, 4, 1);
+      RMXL(4, 4, false);
+      RMXL(4, 4, true);
+      RMXL(4, 4, false);
+      RMXL(4, 4, true);
     }
-  }
-  if (!strcmp(set, "pfg")) {  // cross-group prefetch (the next group's first step before the epilogue stores)
-    const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
-    const int64_t k = (chunks + 192 * 64 - 1) / (192 * 64);
-    const int kg = k % 3 == 0 ? 3 : 4;
-    printf("# k %lld KG %d\n", (long long)k, kg);
-#define PFGV(KG, EB, PF)                                                                                           \
-  vs.push_back(op == FA_OP_AVGM      ? make_rowmajor_pfg<16, 1, 4, KG, FA_OP_AVGM, double, EB, -1, PF>(stack, stride, n, w, ncols, e, bytes, 192) \
-               : op == FA_OP_ADAGRAD ? make_rowmajor_pfg<16, 1, 4, KG, FA_OP_ADAGRAD, double, EB, -1, PF>(stack, stride, n, w, ncols, e, bytes, 192) \
-                                     : make_rowmajor_pfg<16, 1, 4, KG, FA_OP_MEAN, double, EB, -1, PF>(stack, stride, n, w, ncols, e, bytes, 192))
-    for (int rep = 0; rep < 2; ++rep) {
-      if (kg == 3) {
-        if (op == FA_OP_MEAN) { PFGV(3, 2, false); PFGV(3, 2, true); } else { PFGV(3, 4, false); PFGV(3, 4, true); }
-      } else {
-        if (op == FA_OP_MEAN) { PFGV(4, 2, false); PFGV(4, 2, true); } else { PFGV(4, 4, false); PFGV(4, 4, true); }
-      }
-    }
-#undef PFGV
   }
   if (!strcmp(set, "nostore")) {  // NS product geometry (KG 3) with and without its fp32 result stores
     for (int rep = 0; rep < 3; ++rep) {
-      RMXL(3, 2, -1);
+      RME(16, 1, 4, 3, 192, 2);
       Epi<double> e2 = e;
       e2.out32 = nullptr;  // every result store dropped by the descriptor's empty range
-      Variant v = make_rowmajor_xl<16, 1, 4, 3, FA_OP_MEAN, double, 2, -1>(stack, stride, n, w, ncols, e2, bytes, 192);
+      Variant v = make_rowmajor<16, 1, 4, 3, FA_OP_MEAN, double, 2>(stack, stride, n, w, ncols, e2, bytes, 192);
       v.name += " NOSTORE";
       v.checks_output = false;
       vs.push_back(v);
@@ -1101,12 +1061,12 @@ int main(int argc, char** argv) {
   }
   if (!strcmp(set, "xl4")) {  // KG = 4 (C5): whole-line f64 stores at epilogue batch 1 / 2 (no scratch) vs the product
     for (int rep = 0; rep < 2; ++rep) {
-      RMXL(4, 4, 0);
-      RMXL(4, 1, 1);
-      RMXL(4, 2, 1);
-      RMXL(4, 1, 0);
-      vs.push_back(op == FA_OP_AVGM ? make_rowmajor_xl<8, 1, 8, 4, FA_OP_AVGM, double, 4, 1>(stack, stride, n, w, ncols, e, bytes, 192)
-                                    : make_rowmajor_xl<8, 1, 8, 4, FA_OP_ADAGRAD, double, 4, 1>(stack, stride, n, w, ncols, e, bytes, 192));
+      RMXL(4, 4, false);
+      RMXL(4, 1, true);
+      RMXL(4, 2, true);
+      RMXL(4, 1, false);
+      vs.push_back(op == FA_OP_AVGM ? make_rowmajor_xl<8, 1, 8, 4, FA_OP_AVGM, double, 4, true>(stack, stride, n, w, ncols, e, bytes, 192)
+                                    : make_rowmajor_xl<8, 1, 8, 4, FA_OP_ADAGRAD, double, 4, true>(stack, stride, n, w, ncols, e, bytes, 192));
     }
   }
   if (!strcmp(set, "nlb")) {  // narrow strips per wave (LB bytes per lane) vs the product's narrow kernel
@@ -1217,11 +1177,6 @@ int main(int argc, char** argv) {
     RM(16, 1, 4, 3, 192);
     RM(16, 1, 4, 4, 192);
   }
-  if (!strcmp(set, "epinT")) {  // product geometry; built twice (-DFA_EPI_STORE_AUX / LOAD_AUX) for the A/B
-    RM(16, 1, 4, 3, 192);
-    RM(16, 1, 4, 4, 192);
-    RM(8, 1, 8, 4, 192);
-  }
   if (!strcmp(set, "kgrid")) {  // fewer, larger groups from a grid a few blocks off 192 (k = 8 / KG 4 at 196)
     RM(16, 1, 4, 3, 192);
     RM(16, 1, 4, 4, 196);
@@ -1300,12 +1255,10 @@ int main(int argc, char** argv) {
     RME(8, 1, 8, 2, 192, 2);
     RME(8, 1, 8, 4, 192, 2);
   }
-  if (!strcmp(set, "epib")) {  // piece epilogue: per-quad guarded loads (0) vs batched buffer loads of B slots
-    RME(8, 1, 8, 4, 192, 0);
+  if (!strcmp(set, "epib")) {  // piece epilogue: batched buffer loads of B slots
     RME(8, 1, 8, 4, 192, 2);
     RME(8, 1, 8, 4, 192, 4);
     RME(8, 1, 8, 4, 192, 8);
-    RME(8, 1, 8, 3, 192, 0);
     RME(8, 1, 8, 3, 192, 4);
     RME(8, 1, 8, 2, 192, 4);
   }
@@ -1341,13 +1294,11 @@ int main(int argc, char** argv) {
     ROWSG(1, 8, 8, 192);
   }
   if (!strcmp(set, "misc")) {
-    ROWSX(16, 1, 4, 192, false, true);
-    ROWSX(16, 1, 4, 192, true, true);
-    ROWSX(16, 1, 4, 192, false, false);
-    ROWSX(8, 1, 8, 192, false, true);
-    ROWSX(8, 2, 8, 192, false, true);
-    ROWSX(4, 4, 8, 192, false, true);
-    ROWSX(16, 1, 4, 256, true, true);
+    ROWSX(16, 1, 4, 192, true);
+    ROWSX(16, 1, 4, 192, false);
+    ROWSX(8, 1, 8, 192, true);
+    ROWSX(8, 2, 8, 192, true);
+    ROWSX(4, 4, 8, 192, true);
   }
   if (!strcmp(set, "one")) {  // the product geometry against the roofs
     ONESHOTB(16, 1);
@@ -1355,18 +1306,6 @@ int main(int argc, char** argv) {
     ROWSG(16, 1, 4, 224);
     ROWSG(16, 1, 4, 256);
     ROWSG(32, 1, 4, 192);
-  }
-  if (!strcmp(set, "il")) {  // interleaved vs contiguous piece assignment
-    ONESHOTB(16, 1);
-    for (int g : {160, 192, 224, 256}) {
-      ROWSG(16, 1, 4, g);
-      ROWSC(16, 1, 4, g);
-      ROWSG(8, 2, 4, g);
-      ROWSC(8, 2, 4, g);
-    }
-    ROWSG(4, 4, 4, 192);
-    ROWSC(4, 4, 4, 192);
-    ROWSG(16, 2, 4, 192);
   }
   if (!strcmp(set, "inflight")) {  // blocks vs bytes in flight per block
     ONESHOTB(16, 1);

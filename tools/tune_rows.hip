@@ -1,14 +1,15 @@
 // tune_rows.hip — geometry sweep of the row-pointer (device-upload) reduce; TOOL, not product.
 //
 // Built as tools/libtune_rows.so (hipcc --offload-arch=gfx950 -O3 -fPIC -shared tools/tune_rows.hip -o tools/libtune_rows.so) and driven from Python
-// (tools/tune_rows.py) with piece tables built there: the product kernel
-// (fa_device.hpp reduce_kernel_segrows, dynamic piece claiming) at several V / D / W.
+// (tools/tune_rows.py) with piece tables built there: the one-piece-per-claim kernel the product
+// used before (fa_tune_device.hpp reduce_kernel_segrows, dynamic piece claiming) at several
+// V / D / W, and the product kernel (fa_device.hpp reduce_kernel_segrows_rm, claimed row-major
+// groups) at several V / W / KG.
 // Earlier sweeps of this file (profiles/r02/tune_rows/) also held a column-major kernel with
-// the row pointers prefetched one refill ahead (no gain) and a row-major kernel over groups of
-// pieces (slower: one step in flight behind a pointer load).
+// the row pointers prefetched one refill ahead (no gain).
 #include <hip/hip_runtime.h>
 
-#include "../flearn_amd/csrc/fa_device.hpp"
+#include "fa_tune_device.hpp"
 
 namespace {
 using namespace fa;
@@ -46,11 +47,11 @@ extern "C" int tune_rows_launch(int variant, const float* const* rows, int n, co
 
 // split-N variants (fa_device.hpp reduce_kernel_splitn<W, D>) on a [n, stride] stack
 namespace {
-template <int W, int D, bool ST = false>
+template <int W, int D>
 int launch_sn(const float* stack, int64_t stride, int n, const float* w, int64_t ncols, const Epi<double>& e,
               hipStream_t s) {
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
-  hipLaunchKernelGGL((reduce_kernel_splitn<AccF32, double, 0, W, D, true, ST>), dim3((unsigned)chunks), dim3(64 * W), 0,
+  hipLaunchKernelGGL((reduce_kernel_splitn<AccF32, double, 0, W, D, true>), dim3((unsigned)chunks), dim3(64 * W), 0,
                      s, stack, stride, n, w, (int64_t)0, ncols, e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -71,11 +72,6 @@ extern "C" int tune_splitn_launch(int variant, const float* stack, int64_t strid
     case 5: return launch_sn<16, 4>(stack, stride, n, w, ncols, e, s);
     case 6: return launch_sn<2, 16>(stack, stride, n, w, ncols, e, s);
     case 7: return launch_sn<16, 16>(stack, stride, n, w, ncols, e, s);
-    case 8: return launch_sn<4, 8, true>(stack, stride, n, w, ncols, e, s);
-    case 9: return launch_sn<8, 8, true>(stack, stride, n, w, ncols, e, s);
-    case 10: return launch_sn<16, 8, true>(stack, stride, n, w, ncols, e, s);
-    case 11: return launch_sn<8, 16, true>(stack, stride, n, w, ncols, e, s);
-    case 12: return launch_sn<16, 4, true>(stack, stride, n, w, ncols, e, s);
     default: return -1;
   }
 }
@@ -101,11 +97,11 @@ extern "C" int tune_oob_probe(const float* src, uint32_t bytes, int off, float* 
 
 // row-major grouped row-pointer kernel (fa_device.hpp reduce_kernel_segrows_rm<V, W, KG, DN>)
 namespace {
-template <int V, int W, int KG, int DS = 1, bool SG = false, int PFA = 0, int LT = 0>
+template <int V, int W, int KG>
 int launch_rm(const float* const* rows, int n, const float* w, const fa_piece* pieces, int64_t npieces, int grid,
               int* work, const Epi<double>& e, hipStream_t s) {
   if (hipMemsetAsync(work, 0, sizeof(int), s) != hipSuccess) return -3;
-  hipLaunchKernelGGL((reduce_kernel_segrows_rm<AccF32, double, 0, V, W, KG, 16, true, false, DS, SG, PFA, LT>), dim3((unsigned)grid),
+  hipLaunchKernelGGL((reduce_kernel_segrows_rm<AccF32, double, 0, V, W, KG, 16, true>), dim3((unsigned)grid),
                      dim3(64 * W), 0, s, rows, n, w, pieces, npieces, work, e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -123,24 +119,6 @@ extern "C" int tune_rows_rm_launch(int variant, const float* const* rows, int n,
     case 1: return launch_rm<8, 8, 3>(rows, n, w, pieces, npieces, grid, work, e, s);
     case 2: return launch_rm<8, 8, 4>(rows, n, w, pieces, npieces, grid, work, e, s);
     case 3: return launch_rm<16, 4, 2>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 4: return launch_rm<8, 8, 2, 2>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 5: return launch_rm<8, 8, 4, 2>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 6: return launch_rm<16, 4, 2, 2>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 7: return launch_rm<4, 8, 4, 2>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 8: return launch_rm<4, 8, 4, 4>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 9: return launch_rm<8, 8, 2, 1, true>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 10: return launch_rm<16, 4, 2, 1, true>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 11: return launch_rm<8, 8, 3, 1, true>(rows, n, w, pieces, npieces, grid, work, e, s);
-    // translation prefetch PFA steps ahead (round 4, profiles/r04/rows_pmc/)
-    case 12: return launch_rm<8, 8, 2, 1, false, 2>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 13: return launch_rm<8, 8, 2, 1, false, 4>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 14: return launch_rm<8, 8, 2, 1, false, 8>(rows, n, w, pieces, npieces, grid, work, e, s);
-    case 15: return launch_rm<16, 4, 2, 1, false, 4>(rows, n, w, pieces, npieces, grid, work, e, s);
-    // the group's row pointers in LDS (round 5: VERDICT r4 item 4), n <= 1024
-    case 16: return n <= 1024 ? launch_rm<8, 8, 2, 1, false, 0, 1024>(rows, n, w, pieces, npieces, grid, work, e, s) : -1;
-    case 17: return n <= 1024 ? launch_rm<16, 4, 2, 1, false, 0, 1024>(rows, n, w, pieces, npieces, grid, work, e, s) : -1;
-    case 18: return n <= 1024 ? launch_rm<8, 8, 2, 2, false, 0, 1024>(rows, n, w, pieces, npieces, grid, work, e, s) : -1;
-    case 19: return n <= 1024 ? launch_rm<8, 8, 3, 1, false, 0, 1024>(rows, n, w, pieces, npieces, grid, work, e, s) : -1;
     default: return -1;
   }
 }
@@ -175,10 +153,10 @@ extern "C" int tune_rows_rm_avgm(int xl, const float* const* rows, int n, const 
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(work, 0, sizeof(int), s) != hipSuccess) return -3;
   if (xl)
-    hipLaunchKernelGGL((reduce_kernel_segrows_rm<AccF32, double, FA_OP_AVGM, 8, 8, 2, 16, true, false, 1, false, 0, 0, true>),
+    hipLaunchKernelGGL((reduce_kernel_segrows_rm<AccF32, double, FA_OP_AVGM, 8, 8, 2, 16, true, false, true>),
                        dim3((unsigned)grid), dim3(512), 0, s, rows, n, w, pieces, npieces, work, e);
   else
-    hipLaunchKernelGGL((reduce_kernel_segrows_rm<AccF32, double, FA_OP_AVGM, 8, 8, 2, 16, true, false, 1, false, 0, 0, false>),
+    hipLaunchKernelGGL((reduce_kernel_segrows_rm<AccF32, double, FA_OP_AVGM, 8, 8, 2, 16, true, false, false>),
                        dim3((unsigned)grid), dim3(512), 0, s, rows, n, w, pieces, npieces, work, e);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -25,8 +25,7 @@ sys.path.insert(0, str(REPO))
 from flearn_amd import _native as na  # noqa: E402
 from flearn_amd import aggregator as agg  # noqa: E402
 
-VARIANTS = {"w4d8": 0, "w4d16": 1, "w8d8": 2, "w8d16": 3, "w16d8": 4, "w16d4": 5, "w2d16": 6, "w16d16": 7,
-            "st_w4d8": 8, "st_w8d8": 9, "st_w16d8": 10, "st_w8d16": 11, "st_w16d4": 12}
+VARIANTS = {"w4d8": 0, "w4d16": 1, "w8d8": 2, "w8d16": 3, "w16d8": 4, "w16d4": 5, "w2d16": 6, "w16d16": 7}
 
 
 def main():

@@ -17,13 +17,15 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 14
+ABI_VERSION = 15
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
 FA_ERR_ARG, FA_ERR_ALIGN, FA_ERR_LAUNCH = -1, -2, -3
 FA_ERR_SIZE, FA_ERR_UNSUPPORTED, FA_ERR_DATA = -4, -5, -6
 MODE_W32_DIV64, MODE_W32_DIV32, MODE_W64 = 0, 1, 2
+# fa_reduce_f16 modes (FA_MODE_H16_*)
+MODE_H16_NUMPY, MODE_H16_TORCH, MODE_H16_NP16, MODE_H16_W32, MODE_H16_W64 = 0, 1, 2, 3, 4
 OP_MEAN, OP_AVGM, OP_ADAGRAD, OP_YOGI, OP_ADAM, OP_DYN = 0, 1, 2, 3, 4, 5
 SRC_F64, SRC_I64, SRC_F32 = 0, 1, 2  # fa_gather_rows_f64 source kinds
 PREC_F32, PREC_F64 = 0, 1
@@ -37,11 +39,13 @@ EXPORTS = (
     "fa_reduce_f32_splitn",
     "fa_reduce_f64",
     "fa_reduce_i64",
+    "fa_reduce_f16",
     "fa_opt_apply",
     "fa_rows_plan",
     "fa_reduce_f32_rows",
     "fa_gather_rows",
     "fa_gather_rows_f64",
+    "fa_gather_rows_f16",
     "fa_fill_uniform_f32",
     "fa_copy",
     "fa_ipc_handle",
@@ -194,6 +198,7 @@ def load(require_gpu: bool = False):
                                          ctypes.c_int),
                 "fa_reduce_f64": ([P, I64, I32, P, D, I64, I64, P, P], ctypes.c_int),
                 "fa_reduce_i64": ([P, I64, I32, P, D, I64, I64, P, P], ctypes.c_int),
+                "fa_reduce_f16": ([P, I64, I32, I32, P, D, I64, I64, P, P, P, P], ctypes.c_int),
                 "fa_opt_apply": ([I32, ctypes.POINTER(Epilogue), P, P, I64, P, P, P], ctypes.c_int),
                 "fa_rows_plan": ([I32, P, P, I32, I32, P, I64, ctypes.POINTER(I64), ctypes.POINTER(I32)],
                                  ctypes.c_int),
@@ -201,6 +206,7 @@ def load(require_gpu: bool = False):
                                        ctypes.c_int),
                 "fa_gather_rows": ([P, I64, I32, I32, P, P, I32, P], ctypes.c_int),
                 "fa_gather_rows_f64": ([P, I64, I32, P, P, I32, P], ctypes.c_int),
+                "fa_gather_rows_f16": ([P, I64, I32, P, P, I32, P], ctypes.c_int),
                 "fa_fill_uniform_f32": ([P, I64, I32, I64, ctypes.c_uint64, I64, I64, P], ctypes.c_int),
                 "fa_copy": ([P, P, I64, P], ctypes.c_int),
                 "fa_ipc_handle": ([P, P, ctypes.POINTER(I64)], ctypes.c_int),

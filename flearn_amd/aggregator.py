@@ -23,7 +23,7 @@ import torch
 
 from . import _native as na
 from .bucket import BucketPlan, Packer, RowTable, make_plan
-from .semantics import KIND_F32, KIND_F64, KIND_I64, Numerics
+from .semantics import KIND_F16, KIND_F32, KIND_F64, KIND_I64, Numerics
 
 _F64 = np.dtype(np.float64)
 _ONE_W32 = Numerics(KIND_F32, na.MODE_W32_DIV64, np.ones(1, np.float32), 1.0, np.dtype(np.float32), _F64)  # fl32(1.0)
@@ -181,6 +181,37 @@ def reduce_stack_f64(stack, weights, denom, out64, n_clients=None):
     rc = L.fa_reduce_f64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), 0,
                          stack.shape[1], out64.data_ptr(), na.stream_handle(stack.device))
     na.check(rc, "fa_reduce_f64")
+
+
+def reduce_stack_f16(stack, weights, mode, denom, *, out16=None, out32=None, out64=None, col_begin=0, n_cols=None,
+                     n_clients=None) -> None:
+    """Weighted mean of the float16 client stack [N, stride] over columns [col_begin, +n_cols), queued on
+    torch's current stream (fa_reduce_f16; mode: na.MODE_H16_*, see semantics.resolve_half).
+    weights: device float32 (float64 for MODE_H16_W64) — for MODE_H16_NUMPY / _NP16 the float16
+    weights widened.  out64 / out32 / out16 (float64 / float32 / float16 device tensors, any subset):
+    the result in the dtype it is born in, widened exactly, or narrowed through float32 — out16 of a
+    float64 result is fl16(fl32(q)), what load_state_dict into a half module stores."""
+    L = na.lib()
+    _check_cuda(stack, "stack", torch.float16, 2)
+    if stack.stride(1) != 1:
+        raise ValueError("stack rows must be contiguous")
+    n = stack.shape[0] if n_clients is None else n_clients
+    if not 1 <= n <= stack.shape[0]:
+        raise ValueError("n_clients out of range")
+    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
+    if col_begin < 0 or ncols < 0 or col_begin + ncols > stack.shape[1]:
+        raise ValueError("column window out of range")
+    _check_cuda(weights, "weights", torch.float64 if mode == na.MODE_H16_W64 else torch.float32)
+    if weights.numel() < n:
+        raise ValueError("fewer weights than clients")
+    for name, t, dt in (("out16", out16, torch.float16), ("out32", out32, torch.float32), ("out64", out64, torch.float64)):
+        if t is not None:
+            _check_cuda(t, name, dt)
+            if t.numel() < ncols or not t.is_contiguous():
+                raise ValueError(f"{name} too small or not contiguous")
+    rc = L.fa_reduce_f16(stack.data_ptr(), stack.stride(0), n, mode, weights.data_ptr(), float(denom), col_begin, ncols,
+                         _ptr(out16), _ptr(out32), _ptr(out64), na.stream_handle(stack.device))
+    na.check(rc, "fa_reduce_f16")
 
 
 def reduce_stack_i64(stack, weights, denom, out64, n_clients=None):
@@ -651,6 +682,12 @@ class Aggregator:
     scalars for 0-d buffers, torch CPU tensors when the uploads were tensors);
     "float32" — fp32 ndarrays for fp32 keys (the values load_state_dict ends up with);
     "device" — fresh torch CUDA tensors on the first device, fp32 for fp32 keys (no D2H).
+    float16 keys (model.half() clients; fa_reduce_f16): "reference" returns the reference's dtypes —
+    float64, or float16 / float32 for np.float16 / np.float32 weights; "float32" means "what
+    load_state_dict ends up with", which for a float16 key is a float16 array holding fl16(fl32(q))
+    (load_state_dict of the float64 result goes through float: not fl16(q)); "device" returns fresh
+    float16 device tensors with those same values.  Server-fused optimizers and devices=[...] /
+    group= sharding refuse float16 buckets with a TypeError before anything is queued.
 
     devices: the HIP devices the f32 bucket is split over (column shards); each ingests its
     columns through its own PCIe link.  Default: torch's current device only."""
@@ -704,12 +741,40 @@ class Aggregator:
         if t is None:
             if len(self._wcache) >= 64:
                 self._wcache.clear()
-            t = self._wcache[key] = torch.from_numpy(np.ascontiguousarray(nm.weights)).to(device)
+            w = nm.weights
+            if w.dtype == np.float16:  # fa_reduce_f16 takes the float16 weights widened (exact)
+                w = w.astype(np.float32)
+            t = self._wcache[key] = torch.from_numpy(np.ascontiguousarray(w)).to(device)
         return t
+
+    def _refuse_half(self, plan: BucketPlan, server_opt) -> None:
+        """float16 uploads outside what fa_reduce_f16 reproduces raise before anything is queued."""
+        if KIND_F16 not in plan.groups:
+            return
+        if server_opt is not None:
+            raise TypeError(f"float16 uploads: the server-fused {getattr(server_opt, 'name', 'optimizer')} step "
+                            "runs on fp32 models only (aggregate with AVG and update on the client side)")
+        if self._dist or len(self.devices) > 1:
+            raise TypeError("float16 uploads: a float16 bucket is not sharded over devices=[...] / group=")
+
+    def _reduce_f16(self, g, sh, stack, w):
+        """The float16 bucket: "reference" stores the reference's dtype (float64; float16 / float32 for
+        np.float16 / np.float32 weights), "float32" and "device" the float16 values
+        load_state_dict ends up with, fl16(fl32(q))."""
+        nm = g.numerics
+        name, odt = "out16", torch.float16
+        if self.output == "reference" and nm.out_dtype == _F64:
+            name, odt = "out64", torch.float64
+        elif self.output == "reference" and nm.out_dtype == np.float32:
+            name, odt = "out32", torch.float32
+        out = self.packer.device_bucket((name, KIND_F16, sh.index), (sh.width,), odt, sh.device)
+        reduce_stack_f16(stack, w, nm.mode, nm.denom, **{name: out})
+        return out
 
     def ensemble(self, agg_weight_lst, w_local_lst, key_lst=None, server_opt: ServerOptimizer | None = None):
         plan = make_plan(agg_weight_lst, w_local_lst, key_lst)
         self.last_plan = plan
+        self._refuse_half(plan, server_opt)
         if server_opt is None and not self._dist and len(self.devices) == 1 and self.output != "device":
             glob = self._small_round(plan, w_local_lst)
             if glob is not None:
@@ -732,6 +797,8 @@ class Aggregator:
                     w = self._weights(nm, sh.device)
                     if kind == KIND_F32:
                         out = self._reduce_f32(g, sh, stack, w, server_opt, fused, first_means)
+                    elif kind == KIND_F16:
+                        out = self._reduce_f16(g, sh, stack, w)
                     else:
                         out = self.packer.device_bucket(("out64", kind, sh.index), (sh.width,), torch.float64, sh.device)
                         (reduce_stack_f64 if kind == KIND_F64 else reduce_stack_i64)(stack, w, nm.denom, out)
@@ -761,7 +828,8 @@ class Aggregator:
 
         n = plan.n_clients
         total = sum(n * g.stride * np.dtype(_STORE[k]).itemsize for k, g in plan.groups.items())
-        if plan.input_kind != "numpy" or total >= SMALL_BYTES or not plan.groups:
+        # (a float16 bucket takes the general path: its result dtype depends on the output mode)
+        if plan.input_kind != "numpy" or total >= SMALL_BYTES or not plan.groups or KIND_F16 in plan.groups:
             plan.memo[key] = False
             return None
         L, dev = na.lib(), self.device

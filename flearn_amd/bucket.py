@@ -6,6 +6,8 @@ elements).  Here every selected key of every client is flattened into ONE row of
 matrix per arithmetic kind ("bucket"), so a whole aggregation is one kernel launch:
 
     f32 bucket  [N, stride]  fp32 tensors (weights, biases, BN running stats)
+    f16 bucket  [N, stride]  float16 tensors (a model.half() client's uploads): 2-byte elements,
+                             segments on 8-element (16-B) boundaries
     f64 bucket  [N, stride]  float64 tensors, and int64 buffers numpy promotes to float64
     i64 bucket  [N, stride]  int64 buffers under integer weights (stay int64 in numpy)
 
@@ -29,17 +31,20 @@ import numpy as np
 import torch
 
 from . import _native as na
-from .semantics import KIND_F32, KIND_F64, KIND_I64, Numerics, resolve
+from .semantics import KIND_F16, KIND_F32, KIND_F64, KIND_I64, Numerics, resolve, resolve_half
 
 ALIGN = 64  # elements: 256 B for fp32, 512 B for 8-byte kinds
+ALIGN_F16 = 8  # elements: float16 segments start on 16 B (one buffer load of fa_reduce_f16)
+STRIDE_ALIGN_F16 = 128  # elements: the float16 row stride is a multiple of 256 B
 SMALL_BYTES = 4 << 20  # below this, host packing / unpacking runs on the calling thread
 
-_STORE = {KIND_F32: np.float32, KIND_F64: np.float64, KIND_I64: np.int64}
-_TORCH = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64}
+_STORE = {KIND_F32: np.float32, KIND_F64: np.float64, KIND_I64: np.int64, KIND_F16: np.float16}
+_TORCH = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64, np.float16: torch.float16}
 # device-upload dtypes a group's row table takes, and their fa_gather_rows_f64 source kind
 _ROW_SOURCES = {torch.float64: {torch.float64: na.SRC_F64, torch.int64: na.SRC_I64, torch.float32: na.SRC_F32}}
-_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int64: np.int64}
-_FMT = {np.dtype(np.float32): ord("f"), np.dtype(np.float64): ord("d"), np.dtype(np.int64): ord("i")}
+_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int64: np.int64, torch.float16: np.float16}
+_FMT = {np.dtype(np.float32): ord("f"), np.dtype(np.float64): ord("d"), np.dtype(np.int64): ord("i"),
+        np.dtype(np.float16): ord("e")}
 
 
 class AsyncPack:
@@ -303,7 +308,9 @@ def _build_plan(agg_weight_lst, w_local_lst, keys, slow) -> BucketPlan:
                     f"client {n} key {k!r}: {dtn}{list(shn)} does not match client 0's {dt}{list(shape)}"
                 )
         if dt not in numerics_by_dtype:
-            numerics_by_dtype[dt] = resolve(agg_weight_lst, dt)
+            # float16: numpy and torch uploads do not compute the same thing (semantics.resolve_half)
+            numerics_by_dtype[dt] = (resolve_half(agg_weight_lst, ik) if dt == np.float16
+                                     else resolve(agg_weight_lst, dt))
         nm = numerics_by_dtype[dt]
         g = groups.get(nm.kind)
         if g is None:
@@ -317,8 +324,12 @@ def _build_plan(agg_weight_lst, w_local_lst, keys, slow) -> BucketPlan:
         seg = Segment(k, shape, numel, g.stride, dt)
         g.segments.append(seg)
         key_segment[k] = seg
-        g.stride += -(-max(numel, 1) // ALIGN) * ALIGN
+        align = ALIGN_F16 if nm.kind == KIND_F16 else ALIGN
+        g.stride += -(-max(numel, 1) // align) * align
         key_group[k] = nm.kind
+    if KIND_F16 in groups:
+        g = groups[KIND_F16]
+        g.stride = -(-g.stride // STRIDE_ALIGN_F16) * STRIDE_ALIGN_F16
     if len(input_kinds) > 1:
         raise TypeError("mixing numpy arrays and torch tensors in one aggregation is not supported")
     return BucketPlan(keys, groups, key_group, key_segment, len(w_local_lst), input_kinds.pop() if input_kinds else "numpy")
@@ -892,6 +903,10 @@ class RowTable:
             na.check(L.fa_gather_rows_f64(stack.data_ptr(), stack.stride(0), self.shape[0], self.ptrs.data_ptr(),
                                           segs.data_ptr(), len(self.segs), na.stream_handle(self.device)),
                      "fa_gather_rows_f64")
+        elif self.elem_size == 2:  # float16 uploads: gathered, then fa_reduce_f16
+            na.check(L.fa_gather_rows_f16(stack.data_ptr(), stack.stride(0), self.shape[0], self.ptrs.data_ptr(),
+                                          segs.data_ptr(), len(self.segs), na.stream_handle(self.device)),
+                     "fa_gather_rows_f16")
         else:
             na.check(L.fa_gather_rows(stack.data_ptr(), stack.stride(0), self.shape[0], self.elem_size,
                                       self.ptrs.data_ptr(), segs.data_ptr(), len(self.segs),

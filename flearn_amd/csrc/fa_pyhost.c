@@ -42,11 +42,12 @@ static int np_ready(void) {
   return state == 1;
 }
 
-// format class of an ndarray: 'f' f32, 'd' f64, 'i' int64, native byte order; 0 otherwise
+// format class of an ndarray: 'f' f32, 'd' f64, 'i' int64, 'e' f16, native byte order; 0 otherwise
 static char array_class(PyArrayObject *a) {
   PyArray_Descr *d = PyArray_DESCR(a);
   if (PyDataType_ISBYTESWAPPED(d)) return 0;
   switch (d->type_num) {
+    case NPY_FLOAT16: return 'e';
     case NPY_FLOAT32: return 'f';
     case NPY_FLOAT64: return 'd';
     case NPY_INT64: return 'i';
@@ -65,12 +66,13 @@ typedef struct {
   int has_view;
 } Val;
 
-// format class of a buffer: 'f' f32, 'd' f64, 'i' 8-byte signed integer; 0 otherwise
+// format class of a buffer: 'f' f32, 'd' f64, 'i' 8-byte signed integer, 'e' f16; 0 otherwise
 static char format_class(const Py_buffer *v) {
   const char *f = v->format ? v->format : "B";
   if (*f == '@' || *f == '=' || *f == '<') f++;
   if (f[0] == 0 || f[1] != 0) return 0;
   switch (f[0]) {
+    case 'e': return v->itemsize == 2 ? 'e' : 0;
     case 'f': return v->itemsize == 4 ? 'f' : 0;
     case 'd': return v->itemsize == 8 ? 'd' : 0;
     case 'l': case 'q': return v->itemsize == 8 ? 'i' : 0;

@@ -8,7 +8,9 @@
 //     pieces (V KiB x W waves wide; W = 4 for the mean, 8 with a fused optimizer epilogue), rows
 //     pipelined D = 64/(V*W) deep through per-row buffer descriptors (~64 KiB of client rows in
 //     flight per block, whatever the window's width or depth);
-//   * 8-byte kinds (f64 / i64 buckets, small): 4 quads per thread, one row at a time.
+//   * 8-byte kinds (f64 / i64 buckets, small): 4 quads per thread, one row at a time;
+//   * float16 client stacks (fa_reduce_f16): the fp32 one-piece geometry for the same byte width
+//     (launch_reduce_h16), octs of 8 halves per 16-B load.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -503,6 +505,45 @@ int check_common(const X* stack, int64_t stride, int n, const void* w, int64_t c
   return FA_OK;
 }
 
+// float16 client stacks (fa_reduce_f16): the geometry of launch_reduce_window's one-piece-per-block
+// branch for an fp32 window of the same BYTE width — ~0.75 blocks per CU (up to one per CU instead
+// of a nearly empty second round), 4 waves, the narrowest piece (V KiB per wave) that covers the
+// block's share, D = 64/(V*W) rows deep (~64 KiB of client rows in flight per block).  Wider
+// windows are swept piece after piece (column-major).  Vmax follows the sums' registers per oct:
+// 4 VGPRs (f16 sums) 16, 8 (fp32 sums) 8, 16 (f64 sums) 4.  A window of at most one chunk per
+// block runs as single-wave blocks, 16 rows deep.
+template <class HP, int DIV, int V, int W>
+int launch_rows_h16(const uint16_t* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
+                    const EpiH16& e, int64_t grid, hipStream_t s) {
+  constexpr int D = V * W >= kPieceChunks ? 1 : (kPieceChunks / (V * W) > 16 ? 16 : kPieceChunks / (V * W));
+  hipLaunchKernelGGL((reduce_kernel_rows_h16<HP, DIV, V, D, W, kNT>), dim3((unsigned)grid), dim3(64 * W), 0, s, stack,
+                     stride, n, static_cast<const typename HP::w_t*>(w), col0, ncols, e);
+  return launch_check();
+}
+
+template <class HP, int DIV, int VMAX>
+int launch_reduce_h16(const uint16_t* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
+                      const EpiH16& e, hipStream_t s) {
+  constexpr int W = 4;
+  const int cus = device_cus();
+  const int64_t chunks = ((ncols + 7) / 8 + 63) / 64;  // 1-KiB row pieces
+  int64_t grid = (int64_t)(cus * kRowsBlocksPerCU + 0.5);
+  if (chunks > grid * kPieceChunks && chunks <= (int64_t)cus * kPieceChunks)
+    grid = (chunks + kPieceChunks - 1) / kPieceChunks;
+  if (grid < 1) grid = 1;
+  if (grid > chunks) grid = chunks;
+  const int64_t share = (chunks + grid - 1) / grid;  // chunks per block
+  if (share <= 1) return launch_rows_h16<HP, DIV, 1, 1>(stack, stride, n, w, col0, ncols, e, grid, s);
+  if (share <= 1 * W) return launch_rows_h16<HP, DIV, 1, W>(stack, stride, n, w, col0, ncols, e, grid, s);
+  if (share <= 2 * W || VMAX <= 2) return launch_rows_h16<HP, DIV, 2, W>(stack, stride, n, w, col0, ncols, e, grid, s);
+  if (share <= 4 * W || VMAX <= 4) return launch_rows_h16<HP, DIV, 4, W>(stack, stride, n, w, col0, ncols, e, grid, s);
+  if constexpr (VMAX >= 8) {
+    if (share <= 8 * W || VMAX <= 8) return launch_rows_h16<HP, DIV, 8, W>(stack, stride, n, w, col0, ncols, e, grid, s);
+  }
+  if constexpr (VMAX >= 16) return launch_rows_h16<HP, DIV, 16, W>(stack, stride, n, w, col0, ncols, e, grid, s);
+  return fail(FA_ERR_ARG, "no float16 geometry");  // not reached
+}
+
 }  // namespace
 
 namespace {
@@ -584,6 +625,36 @@ int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
   make_epi<double>(nullptr, denom, n_clients, nullptr, out64, &e);
   return launch_reduce<AccI64, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
                                                    n_cols, e, static_cast<hipStream_t>(stream));
+}
+
+int fa_reduce_f16(const void* stack, int64_t row_stride, int32_t n_clients, int32_t mode, const void* weights,
+                  double denom, int64_t col_begin, int64_t n_cols, void* out16, float* out32, double* out64,
+                  void* stream) {
+  if (n_clients <= 0) return fail(FA_ERR_ARG, "n_clients must be >= 1");
+  if (n_cols < 0 || col_begin < 0 || row_stride < col_begin + n_cols) return fail(FA_ERR_ARG, "bad column window");
+  if (!stack || !weights) return fail(FA_ERR_ARG, "null stack or weights");
+  if (!out16 && !out32 && !out64) return fail(FA_ERR_ARG, "no output");
+  if (mode < FA_MODE_H16_NUMPY || mode > FA_MODE_H16_W64) return fail(FA_ERR_ARG, "unknown float16 reduce mode");
+  if (!aligned_to(stack, 16) || row_stride % 8 != 0 || col_begin % 8 != 0)
+    return fail(FA_ERR_ALIGN, "float16 row window not 16-B aligned (stack, row_stride and col_begin in units of 8)");
+  if (!aligned_to(out16, 16) || !aligned_to(out32, 16) || !aligned_to(out64, 32))
+    return fail(FA_ERR_ALIGN, "output arrays must be 16-B (out16, out32) / 32-B (out64) aligned");
+  if (n_cols == 0) return FA_OK;
+  const EpiH16 e{denom, static_cast<uint16_t*>(out16), out32, out64};
+  const uint16_t* st = static_cast<const uint16_t*>(stack);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (mode) {
+    case FA_MODE_H16_NUMPY:
+      return launch_reduce_h16<AccH16Pk, kDivF64, 16>(st, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+    case FA_MODE_H16_TORCH:
+      return launch_reduce_h16<AccH16Torch, kDivF64, 16>(st, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+    case FA_MODE_H16_NP16:
+      return launch_reduce_h16<AccH16Pk, kDivF16, 16>(st, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+    case FA_MODE_H16_W32:
+      return launch_reduce_h16<AccH16W32, kDivF32, 8>(st, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+    default:
+      return launch_reduce_h16<AccH16W64, kDivF64, 4>(st, row_stride, n_clients, weights, col_begin, n_cols, e, s);
+  }
 }
 
 int fa_opt_apply(int32_t prec, const fa_epilogue* epi, const float* local, const void* glob,
@@ -726,6 +797,21 @@ int fa_gather_rows(void* stack, int64_t row_stride, int32_t n_clients, int32_t e
     else
       hipLaunchKernelGGL(gather_rows_kernel<uint64_t>, grid, dim3(kThreads), 0, s, static_cast<uint64_t*>(stack),
                          row_stride, n_clients, reinterpret_cast<const uint64_t* const*>(rows), segs, n_segments, i0);
+    if (int rc = launch_check()) return rc;
+  }
+  return FA_OK;
+}
+
+int fa_gather_rows_f16(void* stack, int64_t row_stride, int32_t n_clients, const void* const* rows,
+                       const int64_t* segs, int32_t n_segments, void* stream) {
+  if (n_clients < 0 || n_segments < 0 || row_stride < 0) return fail(FA_ERR_ARG, "bad gather sizes");
+  if (n_clients == 0 || n_segments == 0) return FA_OK;
+  if (!stack || !rows || !segs) return fail(FA_ERR_ARG, "null gather pointer");
+  for (int32_t i0 = 0; i0 < n_clients; i0 += 65535) {
+    hipLaunchKernelGGL(gather_rows_kernel<uint16_t>,
+                       dim3((unsigned)n_segments, (unsigned)std::min<int32_t>(65535, n_clients - i0)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), static_cast<uint16_t*>(stack), row_stride, n_clients,
+                       reinterpret_cast<const uint16_t* const*>(rows), segs, n_segments, i0);
     if (int rc = launch_check()) return rc;
   }
   return FA_OK;

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 14
+#define FA_ABI_VERSION 15
 
 /* return codes */
 #define FA_OK 0
@@ -138,6 +138,41 @@ int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
                   const int64_t* weights, double denom, int64_t col_begin, int64_t n_cols,
                   double* out64, void* stream);
 
+/* Reduce modes of fa_reduce_f16: how numpy (>= 2) and torch evaluate strategy.py:123-129 on
+ * float16 client tensors, by the upload type and the Python type of the weights a_n.  The two
+ * upload types do NOT compute the same thing.                             */
+#define FA_MODE_H16_NUMPY 0 /* numpy f16 x Python float/int/bool: fl16(fl16(a)*x), f16 sum in list
+                               order, f64 divide by the f64/int64 np.sum -> float64 result        */
+#define FA_MODE_H16_TORCH 1 /* torch f16 x Python float/int: fl16(fl32(fl32(a)*fl32(x))) (two
+                               roundings), f16 sum, f64 divide -> torch.float64 result            */
+#define FA_MODE_H16_NP16 2  /* numpy f16 x np.float16: as NUMPY, then the float16 divide
+                               fl16(fl32(acc)/fl32(W16)), W16 = np.sum (an f16) -> float16 result */
+#define FA_MODE_H16_W32 3   /* numpy f16 x np.float32: fl32(a*fl32(x)), fp32 sum, fp32 divide ->
+                               float32 result (FA_MODE_W32_DIV32 on widened values)               */
+#define FA_MODE_H16_W64 4   /* numpy f16 x np.float64 / np.int64: f64 product, sum and divide ->
+                               float64 result (FA_MODE_W64 on widened values)                     */
+
+/* Weighted mean of float16 client tensors (FA_OP_MEAN only: no epilogue).  Replaces
+ * Strategy.server_ensemble (flearn/common/strategy/strategy.py:123-129) for the float16 keys of
+ * the bucket — what a client that trains with model.half() uploads.  ABI 15.
+ *   stack   : IEEE binary16 bits, row-major [n_clients][row_stride]; 16-byte aligned, row_stride
+ *             and col_begin multiples of 8 elements (FA_ERR_ALIGN otherwise, nothing launched);
+ *             n_cols may be any value >= 0 (odd included).
+ *   weights : device array of n_clients values cast the way numpy / torch cast them: float for
+ *             every mode but FA_MODE_H16_W64 (double).  For FA_MODE_H16_NUMPY / _NP16 the float
+ *             holds the weight already rounded to float16 (np.float16(a) widened, exact: inf for
+ *             |a| > 65504, and the result is then NaN as the reference's is).
+ *   denom   : np.sum(agg_weight_lst) as a double (for _NP16 the float16 sum, widened).
+ *   out64   : [n_cols] the result as double (the reference's dtype for _NUMPY / _TORCH / _W64);
+ *   out32   : [n_cols] the result as float (the reference's dtype for _W32);
+ *   out16   : [n_cols] half bits: the float16 result for _NP16, else fl16(fl32(result)) — what
+ *             load_state_dict of the result into a half module stores.  Sums that leave the half
+ *             range are +-inf, subnormals are kept.  Any of the three may be NULL (not all);
+ *             out16 / out32 16-byte, out64 32-byte aligned.                                     */
+int fa_reduce_f16(const void* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
+                  const void* weights, double denom, int64_t col_begin, int64_t n_cols,
+                  void* out16, float* out32, double* out64, void* stream);
+
 /* Standalone AVGM/OPT update of a received global model (no reduce): the reference location
  * of this math, AVGM.client_receive (avgm.py:38-45) / OPT.client_receive (opt.py:67-76).
  *   prec   : FA_PREC_F64 (glob is double*, v is double*) or FA_PREC_F32 (float*, float*).
@@ -192,6 +227,12 @@ int fa_reduce_f32_rows(const float* const* rows, int32_t n_clients, int32_t mode
  * Any alignment (element-wise copies).                                                         */
 int fa_gather_rows(void* stack, int64_t row_stride, int32_t n_clients, int32_t elem_size,
                    const void* const* rows, const int64_t* segs, int32_t n_segments, void* stream);
+
+/* The same gather for 2-byte elements: device-resident float16 uploads (torch tensors of a
+ * model.half() client, strategy.py:123-129) into the stack fa_reduce_f16 reads.  An entry of
+ * its own so that fa_gather_rows keeps refusing other element sizes.  ABI 15.                 */
+int fa_gather_rows_f16(void* stack, int64_t row_stride, int32_t n_clients, const void* const* rows,
+                       const int64_t* segs, int32_t n_segments, void* stream);
 
 /* The same gather into a float64 stack, converting each segment's source elements as numpy's
  * astype(np.float64) does (what np.multiply(w_local[k], agg_weight) does to an int64 or float32

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 15
+ABI_VERSION = 16
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -61,6 +61,7 @@ EXPORTS = (
     "fa_cache_fence",
     "fa_set_reduce_grid",
     "fa_reduce_windows",
+    "fa_last_launch",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -85,6 +86,13 @@ class Piece(ctypes.Structure):
 
     _fields_ = [("col", ctypes.c_int64), ("seg_off", ctypes.c_int64), ("seg", ctypes.c_int32),
                 ("n_cols", ctypes.c_int32), ("aux", ctypes.c_int64)]
+
+
+class LaunchRecord(ctypes.Structure):
+    """struct fa_launch_record (include/flearn_amd.h)."""
+
+    _fields_ = [("kernel", ctypes.c_char_p), ("grid", ctypes.c_int64), ("launches", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class Epilogue(ctypes.Structure):
@@ -222,6 +230,7 @@ def load(require_gpu: bool = False):
                 "fa_cache_fence": ([I32, P], ctypes.c_int),
                 "fa_set_reduce_grid": ([I32], ctypes.c_int),
                 "fa_reduce_windows": ([I32, I64], ctypes.c_int),
+                "fa_last_launch": ([ctypes.POINTER(LaunchRecord)], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

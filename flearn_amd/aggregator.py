@@ -172,14 +172,26 @@ def reduce_stack(
     na.check(rc, "fa_reduce_f32_splitn" if reorder else "fa_reduce_f32")
 
 
-def reduce_stack_f64(stack, weights, denom, out64, n_clients=None):
+def _window(stack, col_begin, n_cols, out64):
+    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
+    if col_begin < 0 or ncols < 0 or col_begin + ncols > stack.shape[1]:
+        raise ValueError("column window out of range")
+    if out64.numel() < ncols or not out64.is_contiguous():
+        raise ValueError("out64 too small or not contiguous")
+    return ncols
+
+
+def reduce_stack_f64(stack, weights, denom, out64, n_clients=None, *, col_begin=0, n_cols=None):
+    """Weighted mean of the float64 client stack over columns [col_begin, +n_cols) (default: all);
+    out64 is indexed from col_begin."""
     L = na.lib()
     _check_cuda(stack, "stack", torch.float64, 2)
     _check_cuda(weights, "weights", torch.float64)
     _check_cuda(out64, "out64", torch.float64)
     n = stack.shape[0] if n_clients is None else n_clients
-    rc = L.fa_reduce_f64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), 0,
-                         stack.shape[1], out64.data_ptr(), na.stream_handle(stack.device))
+    ncols = _window(stack, col_begin, n_cols, out64)
+    rc = L.fa_reduce_f64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), col_begin,
+                         ncols, out64.data_ptr(), na.stream_handle(stack.device))
     na.check(rc, "fa_reduce_f64")
 
 
@@ -214,14 +226,17 @@ def reduce_stack_f16(stack, weights, mode, denom, *, out16=None, out32=None, out
     na.check(rc, "fa_reduce_f16")
 
 
-def reduce_stack_i64(stack, weights, denom, out64, n_clients=None):
+def reduce_stack_i64(stack, weights, denom, out64, n_clients=None, *, col_begin=0, n_cols=None):
+    """Wrapping int64 weighted sum of the int64 client stack over columns [col_begin, +n_cols)
+    (default: all), then the float64 divide; out64 is indexed from col_begin."""
     L = na.lib()
     _check_cuda(stack, "stack", torch.int64, 2)
     _check_cuda(weights, "weights", torch.int64)
     _check_cuda(out64, "out64", torch.float64)
     n = stack.shape[0] if n_clients is None else n_clients
-    rc = L.fa_reduce_i64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), 0,
-                         stack.shape[1], out64.data_ptr(), na.stream_handle(stack.device))
+    ncols = _window(stack, col_begin, n_cols, out64)
+    rc = L.fa_reduce_i64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), col_begin,
+                         ncols, out64.data_ptr(), na.stream_handle(stack.device))
     na.check(rc, "fa_reduce_i64")
 
 
@@ -268,6 +283,15 @@ def set_reduce_grid(grid: int) -> int:
     if rc < 0:
         na.check(rc, "fa_set_reduce_grid")
     return rc
+
+
+def last_launch():
+    """(kernel, grid, launches) of the calling thread's last reduce call (fa_last_launch): the name
+    of the kernel instantiation launched last, its blocks, and how many launches the call made.
+    kernel is None when the call launched nothing."""
+    rec = na.LaunchRecord()
+    na.check(na.load().fa_last_launch(ctypes.byref(rec)), "fa_last_launch")
+    return (rec.kernel.decode() if rec.kernel else None), rec.grid, rec.launches
 
 
 def fill_uniform(dst: torch.Tensor, seed: int, row_begin: int = 0, col_begin: int = 0,

@@ -36,6 +36,57 @@ int fail(int code, const char* what) {
   return code;
 }
 
+// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* call launched.  A launch
+// stores a pointer and two integers; the name is built once per instantiation (a static of its
+// launch site, as resident_blocks_per_cu keeps its occupancy).
+struct LaunchRecord {
+  const char* kernel = nullptr;
+  int64_t grid = 0;
+  int32_t launches = 0;
+};
+thread_local LaunchRecord g_last_launch;
+
+template <class P, typename T, auto... A>
+struct Inst {};
+template <class HP, auto... A>
+struct HInst {};  // the float16 family has no T
+
+// "family<P,T,args...>": the kernel's demangled symbol name without `fa::`, whitespace and the
+// argument list.  FA_LAUNCH instantiates the kernel from the same argument list, every defaulted
+// template argument spelled out, so the name cannot drift from what is launched.
+std::string make_kernel_name(const char* family, const std::string& f) {
+  // f: pretty_of<Inst<...>>(), "... [I = (anonymous namespace)::Inst<fa::AccF32, float, 0, ...>]"
+  std::string out = family;
+  const size_t b = f.find("Inst<"), e = f.rfind('>');
+  if (b == std::string::npos || e == std::string::npos) return out;
+  for (size_t i = b + 4; i <= e; ++i) {
+    if (f.compare(i, 4, "fa::") == 0) i += 4;
+    if (f[i] != ' ') out += f[i];
+  }
+  return out;
+}
+
+template <class I>
+const char* pretty_of() {
+  return __PRETTY_FUNCTION__;
+}
+
+inline void note_launch(const std::string& kernel, int64_t grid) {
+  g_last_launch.kernel = kernel.c_str();
+  g_last_launch.grid = grid;
+  ++g_last_launch.launches;
+}
+
+#define FA_TARGS(...) __VA_ARGS__
+// FA_LAUNCH(kernel family, (all of its template arguments), grid, block, stream, kernel arguments...)
+// The name is a static of the launch site, built at the first launch of each instantiation.
+#define FA_LAUNCH(family, targs, grid, block, stream, ...)                                                      \
+  do {                                                                                                          \
+    hipLaunchKernelGGL((family<FA_TARGS targs>), dim3((unsigned)(grid)), dim3(block), 0, stream, __VA_ARGS__);  \
+    static const std::string name_ = make_kernel_name(#family, pretty_of<Inst<FA_TARGS targs>>());              \
+    note_launch(name_, (int64_t)(grid));                                                                        \
+  } while (0)
+
 // The runtime epilogue op as a compile-time constant: f(std::integral_constant<int, OP>{}).
 template <class F>
 int with_op(int op, F&& f) {
@@ -116,16 +167,15 @@ template <class P, typename T, int OP, int V, int W>
 int launch_rows(const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
                 int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
   static_assert(V * W <= kPieceChunks, "piece wider than the in-flight budget");
-  hipLaunchKernelGGL((reduce_kernel_rows<P, T, OP, V, kPieceChunks / (V * W), W, kNT>), dim3((unsigned)grid),
-                     dim3(64 * W), 0, s, stack, stride, n, w, col0, ncols, e);
+  FA_LAUNCH(reduce_kernel_rows, (P, T, OP, V, kPieceChunks / (V * W), W, kNT), grid, 64 * W, s, stack, stride, n, w,
+            col0, ncols, e);
   return launch_check();
 }
 
 template <class P, typename T, int OP, int D>
 int launch_narrow(const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
                   int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
-  hipLaunchKernelGGL((reduce_kernel_narrow<P, T, OP, D, 1, kNT>), dim3((unsigned)grid), dim3(64), 0, s, stack, stride,
-                     n, w, col0, ncols, e);
+  FA_LAUNCH(reduce_kernel_narrow, (P, T, OP, D, 1, kNT), grid, 64, s, stack, stride, n, w, col0, ncols, e);
   return launch_check();
 }
 
@@ -138,6 +188,7 @@ int launch_rowmajor(const float* stack, int64_t stride, int n, const typename P:
   // AVGM 100 x 25.6 M: 85.7 vs 84.4%, Adagrad 100 x 86.6 M: 85.1 vs 84.1% (profiles/r02/tune_epiw)
   // — with one group (C2, C4) they do not (84.2 vs 85.0%, 89.7 vs 89.8%, AVGM 83.2 vs 83.4%).
   // Yogi's f64 epilogue does not fit 4 x 16 quads of sums (144 spilled VGPRs)
+  constexpr bool XL = sizeof(T) == 8 && OP != FA_OP_MEAN && KG <= 3;  // the kernel's default, spelled out
   if constexpr (KG <= 3 || (KG == 4 && !(OP == FA_OP_YOGI && sizeof(T) == 8))) {
     const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
     const int64_t k = (chunks + grid * kPieceChunks - 1) / (grid * kPieceChunks);
@@ -147,13 +198,13 @@ int launch_rowmajor(const float* stack, int64_t stride, int n, const typename P:
       // profiles/r03/tune_epib4/): Adagrad 100 x 86.6 M 5315 -> 5272 us, AVGM 100 x 25.6 M
       // 1599 -> 1595 us, AVGM 100 x 11.7 M 711 -> 707 us; the plain mean has no state (+-0.1%)
       constexpr int EB = OP == FA_OP_MEAN ? 2 : 4;
-      hipLaunchKernelGGL((reduce_kernel_rowmajor<P, T, OP, 16, 1, 4, KG, kNT, EB>), dim3((unsigned)grid), dim3(256), 0,
-                         s, stack, stride, n, w, col0, ncols, e);
+      FA_LAUNCH(reduce_kernel_rowmajor, (P, T, OP, 16, 1, 4, KG, kNT, EB, false, XL), grid, 256, s, stack, stride, n, w,
+                col0, ncols, e);
       return launch_check();
     }
   }
-  hipLaunchKernelGGL((reduce_kernel_rowmajor<P, T, OP, 8, 1, 8, KG, kNT>), dim3((unsigned)grid), dim3(512), 0, s,
-                     stack, stride, n, w, col0, ncols, e);
+  FA_LAUNCH(reduce_kernel_rowmajor, (P, T, OP, 8, 1, 8, KG, kNT, 2, false, XL), grid, 512, s, stack, stride, n, w, col0,
+            ncols, e);
   return launch_check();
 }
 
@@ -312,11 +363,11 @@ int launch_reduce_window(const typename P::x_t* stack, int64_t stride, int n, co
     // 8-byte kinds (f64 / i64 buckets: BN counters, float64 state; small): 4 quads per thread,
     // one row at a time, round-balanced grid
     typedef Geometry<P> G;
-    auto kern = reduce_kernel_balanced<P, T, OP, G::kSmallV, G::kSmallU, kNT>;
-    const int64_t slots = (int64_t)cus * resident_blocks_per_cu(kern);
+    const int64_t slots =
+        (int64_t)cus * resident_blocks_per_cu(reduce_kernel_balanced<P, T, OP, G::kSmallV, G::kSmallU, kNT>);
     const int64_t grid = chunks < slots ? chunks : slots;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(kThreads), 0, s, stack, stride, n, wt,
-                       col0, ncols, e);
+    FA_LAUNCH(reduce_kernel_balanced, (P, T, OP, G::kSmallV, G::kSmallU, kNT), grid > 0 ? grid : 1, kThreads, s, stack,
+              stride, n, wt, col0, ncols, e);
     return launch_check();
   }
 }
@@ -385,8 +436,8 @@ int launch_segrows(const float* const* rows, int n, const void* w, const fa_piec
   // fused f64 state: whole-line stores (FedAVGM 100 x ResNet-50 uploads in place 1647.6 -> 1633.8 us,
   // bit-identical: tools/probe_rows_xl.py, profiles/r05/rows_xl/)
   constexpr bool XLS = sizeof(T) == 8 && OP != FA_OP_MEAN;
-  hipLaunchKernelGGL((reduce_kernel_segrows_rm<P, T, OP, kSegV, kSegW, KG, 16, kNT, false, XLS>),
-                     dim3((unsigned)grid), dim3(64 * kSegW), 0, s, rows, n, wt, pieces, npieces, work, e);
+  FA_LAUNCH(reduce_kernel_segrows_rm, (P, T, OP, kSegV, kSegW, KG, 16, kNT, false, XLS), grid, 64 * kSegW, s, rows, n,
+            wt, pieces, npieces, work, e);
   return launch_check();
 }
 
@@ -410,8 +461,8 @@ int launch_splitn(const float* stack, int64_t stride, int n, const void* w, int6
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
   if (n < 2 * kSplitS || n > kSplitMaxN || chunks >= device_cus())  // see kSplitMaxN
     return launch_reduce<P, OP>(stack, stride, n, w, col0, ncols, e, s);
-  hipLaunchKernelGGL((reduce_kernel_splitn<P, T, OP, kSplitW, kSplitD, kNT>), dim3((unsigned)chunks),
-                     dim3(64 * kSplitW), 0, s, stack, stride, n, static_cast<const typename P::w_t*>(w), col0, ncols, e);
+  FA_LAUNCH(reduce_kernel_splitn, (P, T, OP, kSplitW, kSplitD, kNT), chunks, 64 * kSplitW, s, stack, stride, n,
+            static_cast<const typename P::w_t*>(w), col0, ncols, e);
   return launch_check();
 }
 
@@ -518,6 +569,9 @@ int launch_rows_h16(const uint16_t* stack, int64_t stride, int n, const void* w,
   constexpr int D = V * W >= kPieceChunks ? 1 : (kPieceChunks / (V * W) > 16 ? 16 : kPieceChunks / (V * W));
   hipLaunchKernelGGL((reduce_kernel_rows_h16<HP, DIV, V, D, W, kNT>), dim3((unsigned)grid), dim3(64 * W), 0, s, stack,
                      stride, n, static_cast<const typename HP::w_t*>(w), col0, ncols, e);
+  static const std::string name =
+      make_kernel_name("reduce_kernel_rows_h16", pretty_of<HInst<HP, DIV, V, D, W, kNT>>());
+  note_launch(name, grid);
   return launch_check();
 }
 
@@ -567,6 +621,7 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 int fa_reduce_f32(const float* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
                   const void* weights, double denom, int64_t col_begin, int64_t n_cols,
                   const fa_epilogue* epi, float* out32, double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
   int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out32, out64);
   if (rc) return rc;
   if (n_cols == 0) return FA_OK;
@@ -586,6 +641,7 @@ int fa_reduce_f32(const float* stack, int64_t row_stride, int32_t n_clients, int
 int fa_reduce_f32_splitn(const float* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
                          const void* weights, double denom, int64_t col_begin, int64_t n_cols,
                          const fa_epilogue* epi, float* out32, double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
   int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out32, out64);
   if (rc) return rc;
   if (n_cols == 0) return FA_OK;
@@ -604,6 +660,7 @@ int fa_reduce_f32_splitn(const float* stack, int64_t row_stride, int32_t n_clien
 int fa_reduce_f64(const double* stack, int64_t row_stride, int32_t n_clients,
                   const double* weights, double denom, int64_t col_begin, int64_t n_cols,
                   double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
   int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out64, nullptr);
   if (rc) return rc;
   if (n_cols == 0) return FA_OK;
@@ -617,6 +674,7 @@ int fa_reduce_f64(const double* stack, int64_t row_stride, int32_t n_clients,
 int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
                   const int64_t* weights, double denom, int64_t col_begin, int64_t n_cols,
                   double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
   int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out64, nullptr);
   if (rc) return rc;
   if (n_cols == 0) return FA_OK;
@@ -630,6 +688,7 @@ int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
 int fa_reduce_f16(const void* stack, int64_t row_stride, int32_t n_clients, int32_t mode, const void* weights,
                   double denom, int64_t col_begin, int64_t n_cols, void* out16, float* out32, double* out64,
                   void* stream) {
+  g_last_launch = LaunchRecord{};
   if (n_clients <= 0) return fail(FA_ERR_ARG, "n_clients must be >= 1");
   if (n_cols < 0 || col_begin < 0 || row_stride < col_begin + n_cols) return fail(FA_ERR_ARG, "bad column window");
   if (!stack || !weights) return fail(FA_ERR_ARG, "null stack or weights");
@@ -760,6 +819,7 @@ int fa_rows_plan(int32_t n_segments, const int64_t* seg_col, const int64_t* seg_
 int fa_reduce_f32_rows(const float* const* rows, int32_t n_clients, int32_t mode, const void* weights,
                        double denom, const fa_piece* pieces, int64_t n_pieces, int32_t grid, int32_t* work,
                        const fa_epilogue* epi, float* out32, double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
   if (n_clients <= 0) return fail(FA_ERR_ARG, "n_clients must be >= 1");
   if (n_pieces < 0 || (n_pieces > 0 && (!rows || !pieces || !work))) return fail(FA_ERR_ARG, "null rows, pieces or work");
   if (n_pieces > 0 && (grid <= 0 || grid > n_pieces)) return fail(FA_ERR_ARG, "grid must be in [1, n_pieces]");
@@ -840,6 +900,15 @@ int fa_reduce_windows(int32_t op, int64_t n_cols) {
 int fa_set_reduce_grid(int32_t grid) {
   if (grid < 0) return fail(FA_ERR_ARG, "grid must be >= 0");
   return g_reduce_grid.exchange(grid);
+}
+
+int fa_last_launch(fa_launch_record* out) {
+  if (!out) return fail(FA_ERR_ARG, "null launch record");
+  out->kernel = g_last_launch.kernel;
+  out->grid = g_last_launch.grid;
+  out->launches = g_last_launch.launches;
+  out->reserved = 0;
+  return FA_OK;
 }
 
 int fa_copy(void* dst, const void* src, int64_t nbytes, void* stream) {

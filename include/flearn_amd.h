@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 15
+#define FA_ABI_VERSION 16
 
 /* return codes */
 #define FA_OK 0
@@ -268,6 +268,26 @@ int fa_set_reduce_grid(int32_t grid);
  * forced grid) — measured faster, bit-identical (DESIGN.md section 4 finding 26).  For callers
  * that time or profile per launch.  FA_ERR_ARG for an unknown op.  ABI 13.                    */
 int fa_reduce_windows(int32_t op, int64_t n_cols);
+
+/* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
+ * _i64 / _f16 call launched.  For tests and profilers that must know which kernel instantiation a
+ * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
+ * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
+ * pointer and two integers.  No reference counterpart.  ABI 16.
+ *   kernel   : the instantiation launched last, as its demangled symbol name without `fa::`,
+ *              whitespace and the argument list, every template argument included, e.g.
+ *              "reduce_kernel_rows<AccF32,double,0,4,4,4,true>"; a static string, NULL when the
+ *              call launched nothing (an error, an empty window) or no call was made;
+ *   grid     : that launch's blocks;
+ *   launches : kernel launches the call made (fa_reduce_windows' column windows).
+ * out == NULL -> FA_ERR_ARG.                                                                  */
+typedef struct fa_launch_record {
+  const char* kernel;
+  int64_t grid;
+  int32_t launches;
+  int32_t reserved; /* 0 */
+} fa_launch_record;
+int fa_last_launch(fa_launch_record* out);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

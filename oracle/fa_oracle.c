@@ -113,6 +113,57 @@ void ora_sum_w32_splitn(const float* stack, int64_t stride, int32_t n, const flo
   free(apart);
 }
 
+/* The same split order and guard for FA_MODE_W64 (reduce_kernel_splitn<AccF32W64, ...>): f64
+ * products w*(double)x, f64 partial sums and sums of |product|, the same tree, the guard's two
+ * comparisons in f64 (A <= 2|S|, |S| <= 3e38), and the f64 sequential sum for a flagged column.
+ * |p| is the kernel's `p < 0 ? -p : p`. */
+void ora_sum_w64_splitn(const float* stack, int64_t stride, int32_t n, const double* w, int32_t nsplit,
+                        int64_t ncols, double* out, int32_t guard) {
+  const size_t cells = (size_t)(ncols > 0 ? ncols : 1) * (size_t)nsplit;
+  double* part = (double*)malloc(cells * sizeof(double));
+  double* apart = (double*)malloc(cells * sizeof(double));
+  for (int32_t v = 0; v < nsplit; ++v) {
+    const int32_t r0 = (int32_t)((int64_t)v * n / nsplit), r1 = (int32_t)((int64_t)(v + 1) * n / nsplit);
+    double* acc = part + (int64_t)v * ncols;
+    double* aacc = apart + (int64_t)v * ncols;
+    for (int64_t p = 0; p < ncols; ++p) {
+      const double prod = r0 < r1 ? w[r0] * (double)stack[(int64_t)r0 * stride + p] : 0.0;
+      acc[p] = prod;
+      aacc[p] = prod < 0.0 ? -prod : prod;
+    }
+    for (int32_t i = r0 + 1; i < r1; ++i) {
+      const float* row = stack + (int64_t)i * stride;
+      for (int64_t p = 0; p < ncols; ++p) {
+        const double prod = w[i] * (double)row[p];
+        acc[p] = acc[p] + prod;
+        aacc[p] = aacc[p] + (prod < 0.0 ? -prod : prod);
+      }
+    }
+  }
+  for (int32_t h = 1; h < nsplit; h *= 2)
+    for (int32_t v = 0; v + h < nsplit; v += 2 * h)
+      for (int64_t p = 0; p < ncols; ++p) {
+        part[(int64_t)v * ncols + p] = part[(int64_t)v * ncols + p] + part[(int64_t)(v + h) * ncols + p];
+        apart[(int64_t)v * ncols + p] = apart[(int64_t)v * ncols + p] + apart[(int64_t)(v + h) * ncols + p];
+      }
+  for (int64_t p = 0; p < ncols; ++p) {
+    const double sum = part[p], ab = sum < 0.0 ? -sum : sum, two_ab = 2.0 * ab;
+    const int flag = guard && (!(apart[p] <= two_ab) || !(ab <= 3.0e38));
+    if (flag) {  /* the reference's sequential sum */
+      double acc = w[0] * (double)stack[p];
+      for (int32_t i = 1; i < n; ++i) {
+        const double prod = w[i] * (double)stack[(int64_t)i * stride + p];
+        acc = acc + prod;
+      }
+      out[p] = acc;
+    } else {
+      out[p] = sum;
+    }
+  }
+  free(part);
+  free(apart);
+}
+
 /* np.float64 / np.int64 weights on fp32 tensors: promoted to f64 for product and sum. */
 void ora_reduce_w64(const float* stack, int64_t stride, int32_t n, const double* w, double denom,
                     int64_t ncols, double* out64) {

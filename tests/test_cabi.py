@@ -310,6 +310,30 @@ def test_reduce_window_count(L):
         L.fa_set_reduce_grid(prev)
 
 
+def test_launch_record_layout_and_validation(L, tmp_path):
+    """fa_last_launch (ABI 16): ctypes' fa_launch_record has the C compiler's layout; a null record
+    is refused; a call that launches nothing (here: an argument error, then an empty window) leaves
+    an empty record, never an earlier call's."""
+    src = tmp_path / "rec.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "flearn_amd.h"\n'
+                   'int main(void){printf("%zu %zu %zu %zu %zu\\n", sizeof(fa_launch_record),'
+                   'offsetof(fa_launch_record,kernel),offsetof(fa_launch_record,grid),'
+                   'offsetof(fa_launch_record,launches),offsetof(fa_launch_record,reserved));return 0;}\n')
+    exe = tmp_path / "rec"
+    subprocess.run(["gcc", "-I", str(HEADER.parent), str(src), "-o", str(exe)], check=True)
+    c = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
+    R = na.LaunchRecord
+    assert c == [ctypes.sizeof(R), R.kernel.offset, R.grid.offset, R.launches.offset, R.reserved.offset]
+    assert header_define("FA_ABI_VERSION") >= 16
+    assert L.fa_last_launch(None) == header_define("FA_ERR_ARG")
+    for call in (lambda: L.fa_reduce_f32(FAKE, 64, 0, 0, FAKE, 1.0, 0, 64, None, FAKE, None, None),
+                 lambda: L.fa_reduce_f64(FAKE, 64, 2, FAKE, 1.0, 0, 0, FAKE, None)):
+        rec = R(b"stale", 7, 7, 7)
+        call()
+        assert L.fa_last_launch(ctypes.byref(rec)) == 0
+        assert (rec.kernel, rec.grid, rec.launches, rec.reserved) == (None, 0, 0, 0)
+
+
 def test_cache_fence_rejects_an_unknown_kind(L):
     assert L.fa_cache_fence(7, None) == header_define("FA_ERR_ARG")
     assert b"fence" in L.fa_last_error()

@@ -10,7 +10,7 @@ HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 SOURCES = [HERE / "csrc" / "fa_reduce.hip"]
 HOST_SOURCES = [HERE / "csrc" / "fa_wire.cpp"]  # plain host C++ (g++), linked into the same .so
-DEPS = [HERE / "csrc" / "fa_device.hpp"]
+DEPS = [HERE / "csrc" / "fa_device.hpp", HERE / "csrc" / "fa_geometry.hpp"]
 HEADERS = [REPO / "include" / "flearn_amd.h"]
 OUT = HERE / "lib" / "libflearn_amd.so"
 PYHOST_SOURCE = HERE / "csrc" / "fa_pyhost.c"  # Python-object pack helper (ctypes.PyDLL), not C ABI

@@ -1,0 +1,258 @@
+// fa_geometry.hpp — which reduce kernel instantiation runs for a shape, and on what grid.
+//
+// Plain C++17, pure integer decisions: no HIP, no globals, no device queries.  fa_reduce.hip asks
+// these functions for a Plan and turns it into a launch; tests/geometry_probe.cpp asks them on a
+// CPU box (tests/test_geometry_plan.py).  Measured with tools/tune_reduce.hip on MI355X
+// (DESIGN.md §4); every rule carries the measurement behind it.
+#pragma once
+
+#include <stdint.h>
+
+#include <initializer_list>
+
+#include "flearn_amd.h"
+
+namespace fa {
+
+enum Family { kFamRows, kFamNarrow, kFamRowmajor, kFamSplitn, kFamBalanced, kFamRowsH16 };
+
+// One launch: the kernel family, the template arguments its dispatch varies, and the grid.
+struct Plan {
+  int family;
+  int V, W, D;    // quads (float16: octs) per lane and piece, waves per block, rows in flight
+  int KG, EPIB;   // row-major: pieces per group, epilogue slots batched per lane
+  bool wide16;    // row-major: 4 waves x 16 KiB pieces instead of 8 waves x 8 KiB
+  int64_t grid;
+};
+
+// fp32 client stacks.  Fewer blocks than CUs stream best: ~192 blocks on 256 CUs,
+// each keeping ~64 KiB of client rows in flight, equal interleaved pieces of the window.
+//   * several pieces per block (k >= 2): reduce_kernel_rowmajor, 8 waves x 8 KiB per piece,
+//     rows swept once per group of KG pieces (fp32 sums only: f64 sums need 2x the registers);
+//   * one piece per block: reduce_kernel_rows; the piece width and pipeline depth follow the
+//     share s (KiB of every row per block): the narrowest piece that covers s, D = 64/(V*W) rows
+//     deep.  Plain mean: 4 waves x up to 16 KiB per row; fused optimizer epilogues: 8 waves x up
+//     to 8 KiB (half the per-lane state work at every piece end, twice the waves to overlap it).
+constexpr double kRowsBlocksPerCU = 0.75;
+constexpr int kPieceChunks = 64;  // max KiB of a row per block and piece (= W * Vmax)
+
+// 8-byte kinds (f64 / i64 buckets: BN counters, float64 state; small): 4 quads per thread,
+// one row at a time, round-balanced grid
+constexpr int kBalancedV = 4, kBalancedU = 1;
+
+// Split-N geometry (tools/tune_splitn.py, profiles/r02/tune_splitn): one 1-KiB chunk of every row
+// per block, kSplitW client splits (one per wave), each a rolling pipeline kSplitD rows deep.
+// 1000 x 44,416 fp32: 28.7 us vs 50.2 us sequential; 4000 x 44,416: 111 vs 184 us; but
+// 1000 x 1 M (3907 chunks): 738 vs 572 us — so the split form is used only for windows of fewer
+// 1-KiB chunks than CUs, and with at least 2 * kSplitW clients.  And at most kSplitMaxN clients:
+// a reordered fp32 sum differs from the sequential one by about the sequential sum's own rounding
+// error, which grows like sqrt(N), and the contract is <= 1e-6 per tensor.  The exact CPU
+// restatement of both orders (tests/splitn_error.py, profiles/r03/splitn_error.json; LeNet5
+// tensors, 3 seeds x 3 weight kinds x 2 data kinds) puts the worst tensor at 6.2e-7 for N = 256,
+// 7.4e-7 at 512, 2.5e-6 at 1024 (a 6-element bias, MOON weights), 1.3e-6 at 2048 — so 256.
+// Columns whose terms nearly cancel are re-summed in order by the kernel's guard.
+constexpr int kSplitW = 4, kSplitD = 8, kSplitMaxN = 256;
+
+// 1-KiB row pieces of a window of `ncols` elements, `per` of them in a 16-B load
+inline int64_t row_chunks(int64_t ncols, int per = 4) { return ((ncols + per - 1) / per + 63) / 64; }
+
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+inline int64_t natural_grid(int cus) { return (int64_t)(cus * kRowsBlocksPerCU + 0.5); }
+
+// The widest grid of one-piece blocks (reduce_kernel_rows) the geometry below uses: 13/16 of the
+// CUs (100 x 3.2 M columns on 196 blocks 89.7-90.1%, 100 x 3.5 M on 214 blocks 88.6%)
+inline int64_t rows_grid_max(int cus) { return (int64_t)cus * 13 / 16; }
+
+// The grid of one piece per block (fp32 and float16 alike): the forced grid, else ~0.75 blocks
+// per CU; never more blocks than chunks.
+inline int64_t one_piece_grid(int64_t chunks, int cus, int forced) {
+  int64_t grid = forced > 0 ? forced : natural_grid(cus);
+  // a window just wider than one round of full pieces: a few more blocks (up to one per CU)
+  // instead of a second, nearly empty round
+  if (forced <= 0 && chunks > grid * kPieceChunks && chunks <= (int64_t)cus * kPieceChunks)
+    grid = ceil_div(chunks, kPieceChunks);
+  if (grid < 1) grid = 1;
+  if (grid > chunks) grid = chunks;
+  return grid;
+}
+
+// Row-major geometry for windows of several 64-KiB pieces per block (k >= 2): a grid near `target`
+// blocks whose k splits into equal groups of KG in {4, 3, 2} pieces (every step of a group is
+// a real piece).  Returns false when no grid in [160, cus] gives such a k.
+inline bool rowmajor_geometry(int64_t chunks, int cus, int64_t target, int64_t* grid, int* kg) {
+  const int64_t lo = 160 < cus ? 160 : cus, hi = cus;
+  for (int64_t d = 0; d <= hi - lo; ++d) {
+    for (int sgn = 0; sgn < 2; ++sgn) {
+      const int64_t g = sgn ? target - d : target + d;
+      if (g < lo || g > hi || (d == 0 && sgn)) continue;
+      const int64_t k = ceil_div(chunks, g * kPieceChunks);
+      if (k < 2) return false;  // one piece per block: the column-major kernel
+      for (int c : {4, 3, 2}) {  // (5 x 8 quads of sums + the pipeline do not fit 256 VGPRs)
+        if (k % c == 0) {
+          *grid = g;
+          *kg = c;
+          return true;
+        }
+      }
+    }
+  }
+  return false;
+}
+
+// KG for a forced grid: the group size in {4, 3, 2} that wastes the fewest group slots
+inline int kg_for(int64_t k) {
+  int best = 4;
+  int64_t waste = ceil_div(k, 4) * 4 - k;
+  for (int c : {3, 2}) {
+    const int64_t wc = ceil_div(k, c) * c - k;
+    if (wc < waste) {
+      waste = wc;
+      best = c;
+    }
+  }
+  return best;
+}
+
+// Row-major groups of KG pieces on `grid` blocks: the same 64-KiB pieces either as 8 waves x 8 KiB
+// or as 4 waves x 16 KiB.  With several groups per block (k >= 6) 4 waves stream ~1% faster —
+// plain mean 100 x 25.6 M: 86.6 vs 85.8% and 85.1 vs 83.7% on two boxes, 100 x 86.6 M: 83.2 vs
+// 82.3% (profiles/r02/tune_nsgrid); fused AVGM 100 x 25.6 M: 85.7 vs 84.4%, Adagrad 100 x 86.6 M:
+// 85.1 vs 84.1% (profiles/r02/tune_epiw) — with one group (C2, C4) they do not (84.2 vs 85.0%,
+// 89.7 vs 89.8%, AVGM 83.2 vs 83.4%).  Yogi's f64 epilogue does not fit 4 x 16 quads of sums at
+// KG = 4 (144 spilled VGPRs).
+inline Plan rowmajor_plan(int mode, int op, int64_t chunks, int64_t grid, int kg) {
+  const int64_t k = ceil_div(chunks, grid * kPieceChunks);
+  const bool yogi_f64 = op == FA_OP_YOGI && mode != FA_MODE_W32_DIV32;
+  const bool wide16 = k >= 6 && (kg <= 3 || (kg == 4 && !yogi_f64));
+  // 4 x 16: fused epilogues batch the state of 4 slots per lane (EPIB 4) instead of 2: one
+  // process, 9 interleaved rounds, each variant twice (tools/tune_reduce.hip set "epib4",
+  // profiles/r03/tune_epib4/): Adagrad 100 x 86.6 M 5315 -> 5272 us, AVGM 100 x 25.6 M
+  // 1599 -> 1595 us, AVGM 100 x 11.7 M 711 -> 707 us; the plain mean has no state (+-0.1%)
+  const int epib = wide16 && op != FA_OP_MEAN ? 4 : 2;
+  return Plan{kFamRowmajor, wide16 ? 16 : 8, wide16 ? 4 : 8, 1, kg, epib, wide16, grid};
+}
+
+inline Plan rows_plan(int v, int w, int64_t grid) {
+  return Plan{kFamRows, v, w, kPieceChunks / (v * w), 0, 0, false, grid};
+}
+
+// One fp32 stack window (fa_reduce_f32 / fa_reduce_f32_splitn): mode FA_MODE_W32_DIV64 / _DIV32 /
+// _W64, op FA_OP_*, n clients, ncols columns, on `cus` CUs; forced: fa_set_reduce_grid (0 = the
+// geometry chooses); splitn: the caller allows the reordered sum.
+inline Plan plan_f32_window(int mode, int op, int n, int64_t ncols, int cus, int forced, bool splitn) {
+  const int64_t chunks = row_chunks(ncols);
+  if (splitn && n >= 2 * kSplitW && n <= kSplitMaxN && chunks < cus)  // see kSplitMaxN
+    return Plan{kFamSplitn, 0, kSplitW, kSplitD, 0, 0, false, chunks};
+  if (mode != FA_MODE_W64) {  // fp32 sums (every flearn weight type but f64)
+    if (forced > 0 && chunks > (int64_t)forced * kPieceChunks)
+      return rowmajor_plan(mode, op, chunks, forced, kg_for(ceil_div(chunks, (int64_t)forced * kPieceChunks)));
+    // Past one round of the grid: row-major groups.  So also where one piece per block would
+    // take more than rows_grid_max blocks — two pieces per block on a grid near 13/16 of the
+    // CUs instead (100 x 4.19 M columns: 256 one-piece blocks 246 us = 86.0%, 208 blocks x 2
+    // pieces 235 us = 90.2%; tools/width_sweep.py, profiles/r06/width/)
+    const bool past = chunks > (int64_t)cus * kPieceChunks;
+    int64_t g = 0;
+    int kg = 0;
+    if (forced <= 0 && chunks > rows_grid_max(cus) * kPieceChunks &&
+        rowmajor_geometry(chunks, cus, past ? natural_grid(cus) : rows_grid_max(cus), &g, &kg))
+      return rowmajor_plan(mode, op, chunks, g, kg);
+  }
+  int64_t grid = one_piece_grid(chunks, cus, forced);
+  int64_t share = ceil_div(chunks, grid);  // chunks per block
+  if (share <= 2) {
+    // narrow windows (at most two 1-KiB chunks of every row per block: LeNet-sized models, deep
+    // client stacks): reduce_kernel_narrow, one single-wave block per chunk, a D-deep pipeline
+    // with no drain code and the round's weights broadcast from one VGPR.  A 4- or 8-wave
+    // block had work for one or two waves (8-16 KiB in flight per block).  1000 x LeNet5 51.1
+    // -> 31.8 us, 2000 clients 98.3 -> 55.6 us, 400 clients 27.5 -> 15.7 us, 100 clients
+    // 9.8 -> 7.4 us, 300 x 70,001 -> 17.2 us (tools/tune_reduce.hip sets "deep", "deep2";
+    // profiles/r02/tune_deep/).  D: 16 rows below 350 clients (the ramp of a deeper pipeline
+    // does not pay off), 32 below 700, else 40 (48-60 lose: fewer waves' worth of latency
+    // hiding per row than the issue cost of the extra slots).  Same sums, same order.
+    return Plan{kFamNarrow, 1, 1, n < 350 ? 16 : n < 700 ? 32 : 40, 0, 0, false, chunks};
+  }
+  if (op == FA_OP_MEAN) {
+    const int W = 4;
+    // A share just past a power of two leaves about half of every pipeline slot empty (the
+    // piece is V*W KiB wide, `share` KiB of it real, D = 64/(V*W) rows deep).  Where a grid of
+    // at most rows_grid_max blocks makes the share a whole power of two, take that grid: plain
+    // mean 100 x 1.6 M columns 95.1 -> 90.3-90.8 us, 100 x 800 K 48.6 -> 46.5 us; shares >= 60% full
+    // (100 x 2.4 M, 1.2 M, 600 K, 200 K) lose with it, and so do the fused epilogues
+    // (tools/width_sweep.py, profiles/r06/width/)
+    if (forced <= 0) {
+      int64_t cap = W;
+      while (cap < share) cap *= 2;
+      const int64_t g2 = ceil_div(chunks, cap / 2);
+      if (cap > W && share * 5 < cap * 3 && g2 <= rows_grid_max(cus)) {
+        grid = g2;
+        share = ceil_div(chunks, grid);
+      }
+    }
+    int v = 1;  // the narrowest piece that covers the share, at most 16 KiB per wave
+    while (v < 16 && share > v * W) v *= 2;
+    return rows_plan(v, W, grid);
+  }
+  // shares of at most 8 KiB on 4 waves: with 8 waves one quad per lane (V = 1, 8 rows deep)
+  // compiles into register copies — 240 VGPRs, scratch spills and ~1,290 v_mov_b64 per
+  // kernel, for every epilogue — and 100 x 200 K FedAVGM took 45 us, 3x the plain mean
+  if (share <= 4) return rows_plan(1, 4, grid);
+  if (share <= 8) return rows_plan(2, 4, grid);
+  // a share just past 16 or 32 KiB: the grid that makes it a whole 16 / 32 KiB piece, on 4
+  // waves (the mean's rule; 8 waves lose there): FedAVGM 100 x 1.6 M 85.0 -> 88.4-88.6%,
+  // 100 x 800 K 83.0 -> 85.8-86.0%; shares of 9-16 KiB stay on 8 waves (100 x 400 K: 77.9%
+  // against 75.6-75.9% filled on 4; tools/width_sweep.py, profiles/r06/width/fused_*)
+  if (forced <= 0 && share > 16) {
+    const int64_t cap = share <= 32 ? 32 : 64;
+    const int64_t g2 = ceil_div(chunks, cap / 2);
+    if (share * 5 < cap * 3 && g2 <= rows_grid_max(cus)) return rows_plan(ceil_div(chunks, g2) <= 16 ? 4 : 8, 4, g2);
+  }
+  return rows_plan(share <= 16 ? 2 : share <= 32 ? 4 : 8, 8, grid);
+}
+
+// Wide fp32 windows as several launches over consecutive column windows of the same stack
+// (round 5, tools/probe_slabs.py --windows, profiles/r05/c5/: same stack, same allocation,
+// interleaved rounds, two allocations each).  Each window gets its own row-major geometry (grid,
+// KG, groups per block), and these splits measured faster than one launch: fused epilogues at
+// 16 M+ columns in 3 windows — FedOPT-Adagrad 100 x 86.6 M 5282/5270 -> 5190/5211 us, FedAVGM
+// 100 x 86.6 M 5260/5249 -> 5177/5183, FedAVGM 100 x 25.6 M 1561/1564 -> 1542/1544 (2 windows:
+// 1574/1572, slower); plain means of 8-16 M columns in 2 — 100 x 11.7 M 666/665 -> 660/661,
+// 1000 x 11.7 M 6481/6486 -> 6441/6437 (3 windows: 6545).  The plain mean of 25.6 M (NS) stays
+// one launch (2 windows 0.2-0.4% slower), as does 86.6 M (no consistent gain).  Per column the
+// sums and epilogue are unchanged: bit-identical results.  Not with a forced grid (ABI 7), and
+// fp32 sums only.
+inline int window_count(int op, int64_t ncols) {
+  if (op != FA_OP_MEAN) return ncols >= ((int64_t)16 << 20) ? 3 : 1;
+  return (ncols >= ((int64_t)8 << 20) && ncols < ((int64_t)16 << 20)) ? 2 : 1;
+}
+
+// Columns per window of a split into `count`: whole 1-KiB chunks of a row (16-B aligned starts)
+inline int64_t window_width(int64_t ncols, int count) {
+  return count <= 1 ? ncols : ceil_div(ncols, count) / 256 * 256 + 256;
+}
+
+// float16 client stacks (fa_reduce_f16): the one-piece geometry above for an fp32 window of the
+// same BYTE width — ~0.75 blocks per CU (up to one per CU instead of a nearly empty second round),
+// 4 waves, the narrowest piece (V KiB per wave) that covers the block's share, D = 64/(V*W) rows
+// deep, at most 16 (~64 KiB of client rows in flight per block).  Wider windows are swept piece
+// after piece (column-major), D = 1.  vmax follows the sums' registers per oct: 4 VGPRs (f16 sums)
+// 16, 8 (fp32 sums) 8, 16 (f64 sums) 4.  A window of at most one chunk per block runs as
+// single-wave blocks, 16 rows deep.
+inline Plan plan_f16_window(int vmax, int64_t ncols, int cus) {
+  const int64_t chunks = row_chunks(ncols, 8);
+  const int64_t grid = one_piece_grid(chunks, cus, 0);
+  const int64_t share = ceil_div(chunks, grid);  // chunks per block
+  const int w = share <= 1 ? 1 : 4;
+  int v = 1;
+  while (v < vmax && share > v * w) v *= 2;
+  const int d = v * w >= kPieceChunks ? 1 : (kPieceChunks / (v * w) > 16 ? 16 : kPieceChunks / (v * w));
+  return Plan{kFamRowsH16, v, w, d, 0, 0, false, grid};
+}
+
+// 8-byte kinds: one block per chunk up to the resident slots (CUs x the kernel's occupancy)
+inline int64_t balanced_grid(int64_t chunks, int64_t slots) {
+  const int64_t grid = chunks < slots ? chunks : slots;
+  return grid > 0 ? grid : 1;
+}
+
+}  // namespace fa

@@ -2,7 +2,9 @@
 //
 // Host side only: argument validation, dtype/mode dispatch and launches of the gfx950 kernels in
 // fa_device.hpp on the caller's stream.  No allocation, no synchronisation, no host copies.
-// Geometry (measured with tools/tune_reduce.hip on MI355X):
+// Which kernel instantiation runs for a shape, and on what grid, is decided in fa_geometry.hpp
+// (pure integer code, testable without a GPU; measured with tools/tune_reduce.hip on MI355X, see
+// DESIGN.md §4); here one launcher per kernel family turns its Plan into the instantiation:
 //   * fp32 client stacks (every configuration of the hot path): the row-pipelined kernel on
 //     192 blocks (0.75 per CU) with equal interleaved pieces of the window; each block sweeps its
 //     pieces (V KiB x W waves wide; W = 4 for the mean, 8 with a fused optimizer epilogue), rows
@@ -10,7 +12,7 @@
 //     flight per block, whatever the window's width or depth);
 //   * 8-byte kinds (f64 / i64 buckets, small): 4 quads per thread, one row at a time;
 //   * float16 client stacks (fa_reduce_f16): the fp32 one-piece geometry for the same byte width
-//     (launch_reduce_h16), octs of 8 halves per 16-B load.
+//     (plan_f16_window), octs of 8 halves per 16-B load.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -23,6 +25,7 @@
 #include <vector>
 
 #include "fa_device.hpp"
+#include "fa_geometry.hpp"
 #include "flearn_amd.h"
 
 namespace {
@@ -80,12 +83,14 @@ inline void note_launch(const std::string& kernel, int64_t grid) {
 #define FA_TARGS(...) __VA_ARGS__
 // FA_LAUNCH(kernel family, (all of its template arguments), grid, block, stream, kernel arguments...)
 // The name is a static of the launch site, built at the first launch of each instantiation.
-#define FA_LAUNCH(family, targs, grid, block, stream, ...)                                                      \
+// FA_LAUNCH_AS names the tag template first: HInst for the float16 family.
+#define FA_LAUNCH_AS(Tag, family, targs, grid, block, stream, ...)                                              \
   do {                                                                                                          \
     hipLaunchKernelGGL((family<FA_TARGS targs>), dim3((unsigned)(grid)), dim3(block), 0, stream, __VA_ARGS__);  \
-    static const std::string name_ = make_kernel_name(#family, pretty_of<Inst<FA_TARGS targs>>());              \
+    static const std::string name_ = make_kernel_name(#family, pretty_of<Tag<FA_TARGS targs>>());               \
     note_launch(name_, (int64_t)(grid));                                                                        \
   } while (0)
+#define FA_LAUNCH(...) FA_LAUNCH_AS(Inst, __VA_ARGS__)
 
 // The runtime epilogue op as a compile-time constant: f(std::integral_constant<int, OP>{}).
 template <class F>
@@ -105,17 +110,6 @@ int with_op(int op, F&& f) {
 // host side
 // ---------------------------------------------------------------------------------------------
 constexpr bool kNT = true;  // client bytes are read once: non-temporal
-
-template <class P>
-struct Geometry;  // 8-byte kinds only; fp32 stacks use the row pipeline
-template <>
-struct Geometry<AccF64> {
-  static constexpr int kSmallV = 4, kSmallU = 1;
-};
-template <>
-struct Geometry<AccI64> {
-  static constexpr int kSmallV = 4, kSmallU = 1;
-};
 
 int device_cus() {
   static thread_local int dev = -1, cus = 0;
@@ -152,240 +146,105 @@ int launch_check() {
   return FA_OK;
 }
 
-// fp32 client stacks.  Fewer blocks than CUs stream best: ~192 blocks on 256 CUs,
-// each keeping ~64 KiB of client rows in flight, equal interleaved pieces of the window.
-//   * several pieces per block (k >= 2): reduce_kernel_rowmajor, 8 waves x 8 KiB per piece,
-//     rows swept once per group of KG pieces (fp32 sums only: f64 sums need 2x the registers);
-//   * one piece per block: reduce_kernel_rows; the piece width and pipeline depth follow the
-//     share s (KiB of every row per block): the narrowest piece that covers s, D = 64/(V*W) rows
-//     deep.  Plain mean: 4 waves x up to 16 KiB per row; fused optimizer epilogues: 8 waves x up
-//     to 8 KiB (half the per-lane state work at every piece end, twice the waves to overlap it).
-constexpr double kRowsBlocksPerCU = 0.75;
-constexpr int kPieceChunks = 64;  // max KiB of a row per block and piece (= W * Vmax)
+// fa_set_reduce_grid: 0 = the geometry (fa_geometry.hpp) chooses the grid
+std::atomic<int> g_reduce_grid{0};
 
-template <class P, typename T, int OP, int V, int W>
-int launch_rows(const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
-                int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
-  static_assert(V * W <= kPieceChunks, "piece wider than the in-flight budget");
-  FA_LAUNCH(reduce_kernel_rows, (P, T, OP, V, kPieceChunks / (V * W), W, kNT), grid, 64 * W, s, stack, stride, n, w,
-            col0, ncols, e);
-  return launch_check();
+// One column window of a client stack: the arguments every stack kernel takes, in their order.
+template <class P, typename T>
+struct Window {
+  const typename P::x_t* stack;
+  int64_t stride;
+  int n;
+  const typename P::w_t* w;
+  int64_t col0, ncols;
+  Epi<T> e;
+};
+#define FA_WIN(a) a.stack, a.stride, a.n, a.w, a.col0, a.ncols, a.e
+
+// The launchers below turn a Plan (fa_geometry.hpp) into the template instantiation it names, one
+// switch per kernel family.  They choose nothing: a plan value with no shipped instantiation is an
+// error, never another kernel.
+int no_kernel(const char* family) {
+  return fail(FA_ERR_ARG, (std::string("no shipped ") + family + " instantiation for the plan").c_str());
 }
 
-template <class P, typename T, int OP, int D>
-int launch_narrow(const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
-                  int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
-  FA_LAUNCH(reduce_kernel_narrow, (P, T, OP, D, 1, kNT), grid, 64, s, stack, stride, n, w, col0, ncols, e);
-  return launch_check();
+// one piece per block: 4 waves for the mean; fused epilogues 4 waves up to 8 KiB and for the
+// filled 16 / 32 KiB pieces, else 8 waves
+template <int OP, class P, typename T>
+int launch_rows(const Plan& p, const Window<P, T>& a, hipStream_t s) {
+  constexpr bool kMean = OP == FA_OP_MEAN;
+#define FA_ROWS(V, W, SHIPPED)                                                                                      \
+  case V * 100 + W:                                                                                                 \
+    if constexpr (SHIPPED) {                                                                                        \
+      static_assert(V * W <= kPieceChunks, "piece wider than the in-flight budget");                                \
+      FA_LAUNCH(reduce_kernel_rows, (P, T, OP, V, kPieceChunks / (V * W), W, kNT), p.grid, 64 * W, s, FA_WIN(a));   \
+      return launch_check();                                                                                        \
+    }                                                                                                               \
+    break
+  switch (p.V * 100 + p.W) {
+    FA_ROWS(1, 4, true);
+    FA_ROWS(2, 4, true);
+    FA_ROWS(4, 4, true);
+    FA_ROWS(8, 4, true);
+    FA_ROWS(16, 4, kMean);
+    FA_ROWS(2, 8, !kMean);
+    FA_ROWS(4, 8, !kMean);
+    FA_ROWS(8, 8, !kMean);
+  }
+#undef FA_ROWS
+  return no_kernel("reduce_kernel_rows");
 }
 
-template <class P, typename T, int OP, int KG>
-int launch_rowmajor(const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
-                    int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
-  // The same 64-KiB pieces either as 8 waves x 8 KiB or as 4 waves x 16 KiB.  With several groups
-  // per block (k >= 6) 4 waves stream ~1% faster — plain mean 100 x 25.6 M: 86.6 vs 85.8% and
-  // 85.1 vs 83.7% on two boxes, 100 x 86.6 M: 83.2 vs 82.3% (profiles/r02/tune_nsgrid); fused
-  // AVGM 100 x 25.6 M: 85.7 vs 84.4%, Adagrad 100 x 86.6 M: 85.1 vs 84.1% (profiles/r02/tune_epiw)
-  // — with one group (C2, C4) they do not (84.2 vs 85.0%, 89.7 vs 89.8%, AVGM 83.2 vs 83.4%).
-  // Yogi's f64 epilogue does not fit 4 x 16 quads of sums (144 spilled VGPRs)
+template <int OP, class P, typename T>
+int launch_narrow(const Plan& p, const Window<P, T>& a, hipStream_t s) {
+#define FA_NARROW(D)                                                                  \
+  case D:                                                                             \
+    FA_LAUNCH(reduce_kernel_narrow, (P, T, OP, D, 1, kNT), p.grid, 64, s, FA_WIN(a)); \
+    return launch_check()
+  switch (p.D) {
+    FA_NARROW(16);
+    FA_NARROW(32);
+    FA_NARROW(40);
+  }
+#undef FA_NARROW
+  return no_kernel("reduce_kernel_narrow");
+}
+
+template <int OP, int KG, class P, typename T>
+int launch_rowmajor_kg(const Plan& p, const Window<P, T>& a, hipStream_t s) {
   constexpr bool XL = sizeof(T) == 8 && OP != FA_OP_MEAN && KG <= 3;  // the kernel's default, spelled out
-  if constexpr (KG <= 3 || (KG == 4 && !(OP == FA_OP_YOGI && sizeof(T) == 8))) {
-    const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
-    const int64_t k = (chunks + grid * kPieceChunks - 1) / (grid * kPieceChunks);
-    if (k >= 6) {
-      // fused epilogues batch the state of 4 slots per lane (EPIB 4) instead of 2: one process,
-      // 9 interleaved rounds, each variant twice (tools/tune_reduce.hip set "epib4",
-      // profiles/r03/tune_epib4/): Adagrad 100 x 86.6 M 5315 -> 5272 us, AVGM 100 x 25.6 M
-      // 1599 -> 1595 us, AVGM 100 x 11.7 M 711 -> 707 us; the plain mean has no state (+-0.1%)
-      constexpr int EB = OP == FA_OP_MEAN ? 2 : 4;
-      FA_LAUNCH(reduce_kernel_rowmajor, (P, T, OP, 16, 1, 4, KG, kNT, EB, false, XL), grid, 256, s, stack, stride, n, w,
-                col0, ncols, e);
+  constexpr int EB = OP == FA_OP_MEAN ? 2 : 4;                        // EPIB of the 4 x 16 form
+  if (!p.wide16 && p.EPIB == 2) {
+    FA_LAUNCH(reduce_kernel_rowmajor, (P, T, OP, 8, 1, 8, KG, kNT, 2, false, XL), p.grid, 512, s, FA_WIN(a));
+    return launch_check();
+  }
+  // Yogi's f64 epilogue has no 4 x 16 form at KG = 4 (fa_geometry.hpp rowmajor_plan)
+  if constexpr (KG <= 3 || !(OP == FA_OP_YOGI && sizeof(T) == 8)) {
+    if (p.wide16 && p.EPIB == EB) {
+      FA_LAUNCH(reduce_kernel_rowmajor, (P, T, OP, 16, 1, 4, KG, kNT, EB, false, XL), p.grid, 256, s, FA_WIN(a));
       return launch_check();
     }
   }
-  FA_LAUNCH(reduce_kernel_rowmajor, (P, T, OP, 8, 1, 8, KG, kNT, 2, false, XL), grid, 512, s, stack, stride, n, w, col0,
-            ncols, e);
+  return no_kernel("reduce_kernel_rowmajor");
+}
+
+template <int OP, class P, typename T>
+int launch_rowmajor(const Plan& p, const Window<P, T>& a, hipStream_t s) {
+  if constexpr (sizeof(typename P::acc_t) == 4) {  // fp32 sums only
+    switch (p.KG) {
+      case 2: return launch_rowmajor_kg<OP, 2>(p, a, s);
+      case 3: return launch_rowmajor_kg<OP, 3>(p, a, s);
+      case 4: return launch_rowmajor_kg<OP, 4>(p, a, s);
+    }
+  }
+  return no_kernel("reduce_kernel_rowmajor");
+}
+
+template <int OP, class P, typename T>
+int launch_splitn(const Plan& p, const Window<P, T>& a, hipStream_t s) {
+  if (p.W != kSplitW || p.D != kSplitD) return no_kernel("reduce_kernel_splitn");
+  FA_LAUNCH(reduce_kernel_splitn, (P, T, OP, kSplitW, kSplitD, kNT), p.grid, 64 * kSplitW, s, FA_WIN(a));
   return launch_check();
-}
-
-template <class P, typename T, int OP>
-int launch_rowmajor_kg(int kg, const float* stack, int64_t stride, int n, const typename P::w_t* w, int64_t col0,
-                       int64_t ncols, const Epi<T>& e, int64_t grid, hipStream_t s) {
-  switch (kg) {
-    case 2: return launch_rowmajor<P, T, OP, 2>(stack, stride, n, w, col0, ncols, e, grid, s);
-    case 3: return launch_rowmajor<P, T, OP, 3>(stack, stride, n, w, col0, ncols, e, grid, s);
-    default: return launch_rowmajor<P, T, OP, 4>(stack, stride, n, w, col0, ncols, e, grid, s);
-  }
-}
-
-// Row-major geometry for windows of several 64-KiB pieces per block (k >= 2): a grid near 192
-// blocks whose k splits into equal groups of KG in {4, 3, 2} pieces (every step of a group is
-// a real piece).  Returns false when no grid in [160, cus] gives such a k.
-bool rowmajor_geometry(int64_t chunks, int cus, int64_t target, int64_t* grid, int* kg) {
-  const int64_t lo = 160 < cus ? 160 : cus, hi = cus;
-  for (int64_t d = 0; d <= hi - lo; ++d) {
-    for (int sgn = 0; sgn < 2; ++sgn) {
-      const int64_t g = sgn ? target - d : target + d;
-      if (g < lo || g > hi || (d == 0 && sgn)) continue;
-      const int64_t k = (chunks + g * kPieceChunks - 1) / (g * kPieceChunks);
-      if (k < 2) return false;  // one piece per block: the column-major kernel
-      for (int c : {4, 3, 2}) {  // (5 x 8 quads of sums + the pipeline do not fit 256 VGPRs)
-        if (k % c == 0) {
-          *grid = g;
-          *kg = c;
-          return true;
-        }
-      }
-    }
-  }
-  return false;
-}
-
-// The widest grid of one-piece blocks (reduce_kernel_rows) the geometry below uses: 13/16 of the
-// CUs (100 x 3.2 M columns on 196 blocks 89.7-90.1%, 100 x 3.5 M on 214 blocks 88.6%)
-int64_t rows_grid_max(int cus) { return (int64_t)cus * 13 / 16; }
-
-// fa_set_reduce_grid: 0 = the geometry below chooses the grid
-std::atomic<int> g_reduce_grid{0};
-
-// KG for a forced grid: the group size in {4, 3, 2} that wastes the fewest group slots
-int kg_for(int64_t k) {
-  int best = 4;
-  int64_t waste = (k + 3) / 4 * 4 - k;
-  for (int c : {3, 2}) {
-    const int64_t wc = (k + c - 1) / c * c - k;
-    if (wc < waste) {
-      waste = wc;
-      best = c;
-    }
-  }
-  return best;
-}
-
-template <class P, typename T, int OP>
-int launch_reduce_window(const typename P::x_t* stack, int64_t stride, int n, const void* w, int64_t col0,
-                         int64_t ncols, const Epi<T>& e, hipStream_t s) {
-  const typename P::w_t* wt = static_cast<const typename P::w_t*>(w);
-  const int cus = device_cus();
-  const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;  // 1-KiB row pieces
-  const int forced = g_reduce_grid.load(std::memory_order_relaxed);
-  if constexpr (sizeof(typename P::x_t) == 4) {
-    if constexpr (sizeof(typename P::acc_t) == 4) {  // fp32 sums (every flearn weight type but f64)
-      int64_t g = 0;
-      int kg = 0;
-      if (forced > 0 && chunks > (int64_t)forced * kPieceChunks) {
-        g = forced;
-        kg = kg_for((chunks + g * kPieceChunks - 1) / (g * kPieceChunks));
-        return launch_rowmajor_kg<P, T, OP>(kg, stack, stride, n, wt, col0, ncols, e, g, s);
-      }
-      // Past one round of the grid: row-major groups.  So also where one piece per block would
-      // take more than rows_grid_max blocks — two pieces per block on a grid near 13/16 of the
-      // CUs instead (100 x 4.19 M columns: 256 one-piece blocks 246 us = 86.0%, 208 blocks x 2
-      // pieces 235 us = 90.2%; tools/width_sweep.py, profiles/r06/width/)
-      const bool past = chunks > (int64_t)cus * kPieceChunks;
-      if (forced <= 0 && chunks > rows_grid_max(cus) * kPieceChunks &&
-          rowmajor_geometry(chunks, cus, past ? (int64_t)(cus * kRowsBlocksPerCU + 0.5) : (int64_t)cus * 13 / 16, &g,
-                            &kg)) {
-        return launch_rowmajor_kg<P, T, OP>(kg, stack, stride, n, wt, col0, ncols, e, g, s);
-      }
-    }
-    int64_t grid = forced > 0 ? forced : (int64_t)(cus * kRowsBlocksPerCU + 0.5);
-    // a window just wider than one round of full pieces: a few more blocks (up to one per CU)
-    // instead of a second, nearly empty round
-    if (forced <= 0 && chunks > grid * kPieceChunks && chunks <= (int64_t)cus * kPieceChunks)
-      grid = (chunks + kPieceChunks - 1) / kPieceChunks;
-    if (grid < 1) grid = 1;
-    if (grid > chunks) grid = chunks;
-    int64_t share = (chunks + grid - 1) / grid;  // chunks per block
-    if (share <= 2) {
-      // narrow windows (at most two 1-KiB chunks of every row per block: LeNet-sized models, deep
-      // client stacks): reduce_kernel_narrow, one single-wave block per chunk, a D-deep pipeline
-      // with no drain code and the round's weights broadcast from one VGPR.  A 4- or 8-wave
-      // block had work for one or two waves (8-16 KiB in flight per block).  1000 x LeNet5 51.1
-      // -> 31.8 us, 2000 clients 98.3 -> 55.6 us, 400 clients 27.5 -> 15.7 us, 100 clients
-      // 9.8 -> 7.4 us, 300 x 70,001 -> 17.2 us (tools/tune_reduce.hip sets "deep", "deep2";
-      // profiles/r02/tune_deep/).  D: 16 rows below 350 clients (the ramp of a deeper pipeline
-      // does not pay off), 32 below 700, else 40 (48-60 lose: fewer waves' worth of latency
-      // hiding per row than the issue cost of the extra slots).  Same sums, same order.
-      const int64_t g1 = chunks;
-      if (n < 350) return launch_narrow<P, T, OP, 16>(stack, stride, n, wt, col0, ncols, e, g1, s);
-      if (n < 700) return launch_narrow<P, T, OP, 32>(stack, stride, n, wt, col0, ncols, e, g1, s);
-      return launch_narrow<P, T, OP, 40>(stack, stride, n, wt, col0, ncols, e, g1, s);
-    }
-    if constexpr (OP == FA_OP_MEAN) {
-      constexpr int W = 4;
-      // A share just past a power of two leaves about half of every pipeline slot empty (the
-      // piece is V*W KiB wide, `share` KiB of it real, D = 64/(V*W) rows deep).  Where a grid of
-      // at most rows_grid_max blocks makes the share a whole power of two, take that grid: plain
-      // mean 100 x 1.6 M columns 95.1 -> 90.3-90.8 us, 100 x 800 K 48.6 -> 46.5 us; shares >= 60% full
-      // (100 x 2.4 M, 1.2 M, 600 K, 200 K) lose with it, and so do the fused epilogues
-      // (tools/width_sweep.py, profiles/r06/width/)
-      if (forced <= 0) {
-        int64_t cap = W;
-        while (cap < share) cap *= 2;
-        const int64_t g2 = (chunks + cap / 2 - 1) / (cap / 2);
-        if (cap > W && share * 5 < cap * 3 && g2 <= rows_grid_max(cus)) {
-          grid = g2;
-          share = (chunks + grid - 1) / grid;
-        }
-      }
-      if (share <= 1 * W) return launch_rows<P, T, OP, 1, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      if (share <= 2 * W) return launch_rows<P, T, OP, 2, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      if (share <= 4 * W) return launch_rows<P, T, OP, 4, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      if (share <= 8 * W) return launch_rows<P, T, OP, 8, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      return launch_rows<P, T, OP, 16, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-    } else {
-      constexpr int W = 8;
-      // shares of at most 8 KiB on 4 waves: with 8 waves one quad per lane (V = 1, 8 rows deep)
-      // compiles into register copies — 240 VGPRs, scratch spills and ~1,290 v_mov_b64 per
-      // kernel, for every epilogue — and 100 x 200 K FedAVGM took 45 us, 3x the plain mean
-      if (share <= 4) return launch_rows<P, T, OP, 1, 4>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      if (share <= 8) return launch_rows<P, T, OP, 2, 4>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      // a share just past 16 or 32 KiB: the grid that makes it a whole 16 / 32 KiB piece, on 4
-      // waves (the mean's rule; 8 waves lose there): FedAVGM 100 x 1.6 M 85.0 -> 88.4-88.6%,
-      // 100 x 800 K 83.0 -> 85.8-86.0%; shares of 9-16 KiB stay on 8 waves (100 x 400 K: 77.9%
-      // against 75.6-75.9% filled on 4; tools/width_sweep.py, profiles/r06/width/fused_*)
-      if (forced <= 0 && share > 16) {
-        const int64_t cap = share <= 32 ? 32 : 64;
-        const int64_t g2 = (chunks + cap / 2 - 1) / (cap / 2);
-        if (share * 5 < cap * 3 && g2 <= rows_grid_max(cus)) {
-          grid = g2;
-          share = (chunks + grid - 1) / grid;
-          if (share <= 16) return launch_rows<P, T, OP, 4, 4>(stack, stride, n, wt, col0, ncols, e, grid, s);
-          return launch_rows<P, T, OP, 8, 4>(stack, stride, n, wt, col0, ncols, e, grid, s);
-        }
-      }
-      if (share <= 2 * W) return launch_rows<P, T, OP, 2, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      if (share <= 4 * W) return launch_rows<P, T, OP, 4, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-      return launch_rows<P, T, OP, 8, W>(stack, stride, n, wt, col0, ncols, e, grid, s);
-    }
-  } else {
-    // 8-byte kinds (f64 / i64 buckets: BN counters, float64 state; small): 4 quads per thread,
-    // one row at a time, round-balanced grid
-    typedef Geometry<P> G;
-    const int64_t slots =
-        (int64_t)cus * resident_blocks_per_cu(reduce_kernel_balanced<P, T, OP, G::kSmallV, G::kSmallU, kNT>);
-    const int64_t grid = chunks < slots ? chunks : slots;
-    FA_LAUNCH(reduce_kernel_balanced, (P, T, OP, G::kSmallV, G::kSmallU, kNT), grid > 0 ? grid : 1, kThreads, s, stack,
-              stride, n, wt, col0, ncols, e);
-    return launch_check();
-  }
-}
-
-// Wide fp32 windows as several launches over consecutive column windows of the same stack
-// (round 5, tools/probe_slabs.py --windows, profiles/r05/c5/: same stack, same allocation,
-// interleaved rounds, two allocations each).  Each window gets its own row-major geometry (grid,
-// KG, groups per block), and these splits measured faster than one launch: fused epilogues at
-// 16 M+ columns in 3 windows — FedOPT-Adagrad 100 x 86.6 M 5282/5270 -> 5190/5211 us, FedAVGM
-// 100 x 86.6 M 5260/5249 -> 5177/5183, FedAVGM 100 x 25.6 M 1561/1564 -> 1542/1544 (2 windows:
-// 1574/1572, slower); plain means of 8-16 M columns in 2 — 100 x 11.7 M 666/665 -> 660/661,
-// 1000 x 11.7 M 6481/6486 -> 6441/6437 (3 windows: 6545).  The plain mean of 25.6 M (NS) stays
-// one launch (2 windows 0.2-0.4% slower), as does 86.6 M (no consistent gain).  Per column the
-// sums and epilogue are unchanged: bit-identical results.  Not with a forced grid (ABI 7).
-template <int OP>
-int window_count(int64_t ncols) {
-  if (OP != FA_OP_MEAN) return ncols >= ((int64_t)16 << 20) ? 3 : 1;
-  return (ncols >= ((int64_t)8 << 20) && ncols < ((int64_t)16 << 20)) ? 2 : 1;
 }
 
 template <typename T>
@@ -400,19 +259,67 @@ Epi<T> epi_at(const Epi<T>& e, int64_t c) {  // the epilogue's per-column arrays
   return o;
 }
 
+// fa_reduce_f32 / fa_reduce_f32_splitn (reorder): the window split and each window's plan come
+// from fa_geometry.hpp, the family's launcher instantiates it.
 template <class P, int OP, typename T>
-int launch_reduce(const typename P::x_t* stack, int64_t stride, int n, const void* w, int64_t col0,
+int launch_reduce(int mode, bool reorder, const float* stack, int64_t stride, int n, const void* w, int64_t col0,
                   int64_t ncols, const Epi<T>& e, hipStream_t s) {
-  int S = 1;
-  if constexpr (sizeof(typename P::x_t) == 4 && sizeof(typename P::acc_t) == 4)
-    if (g_reduce_grid.load(std::memory_order_relaxed) <= 0) S = window_count<OP>(ncols);
-  if (S <= 1) return launch_reduce_window<P, T, OP>(stack, stride, n, w, col0, ncols, e, s);
-  const int64_t width = (ncols + S - 1) / S / 256 * 256 + 256;  // 1-KiB chunks of a row: 16-B aligned
+  const int cus = device_cus();
+  const int forced = g_reduce_grid.load(std::memory_order_relaxed);
+  const int S = mode != FA_MODE_W64 && forced <= 0 ? window_count(OP, ncols) : 1;
+  const int64_t width = window_width(ncols, S);
   for (int64_t c = 0; c < ncols; c += width) {
     const int64_t wc = ncols - c < width ? ncols - c : width;
-    if (int rc = launch_reduce_window<P, T, OP>(stack, stride, n, w, col0 + c, wc, epi_at(e, c), s)) return rc;
+    const Window<P, T> a{stack, stride, n, static_cast<const typename P::w_t*>(w), col0 + c, wc, epi_at(e, c)};
+    const Plan p = plan_f32_window(mode, OP, n, wc, cus, forced, reorder && S == 1);
+    int rc;
+    switch (p.family) {
+      case kFamRows: rc = launch_rows<OP>(p, a, s); break;
+      case kFamNarrow: rc = launch_narrow<OP>(p, a, s); break;
+      case kFamRowmajor: rc = launch_rowmajor<OP>(p, a, s); break;
+      case kFamSplitn: rc = launch_splitn<OP>(p, a, s); break;
+      default: rc = no_kernel("fp32 stack");
+    }
+    if (rc) return rc;
   }
   return FA_OK;
+}
+
+// fa_reduce_f64 / fa_reduce_i64: the occupancy query stays here, the grid rule is balanced_grid's
+template <class P>
+int launch_balanced(const Window<P, double>& a, hipStream_t s) {
+  const auto kernel = reduce_kernel_balanced<P, double, FA_OP_MEAN, kBalancedV, kBalancedU, kNT>;
+  const int64_t slots = (int64_t)device_cus() * resident_blocks_per_cu(kernel);
+  FA_LAUNCH(reduce_kernel_balanced, (P, double, FA_OP_MEAN, kBalancedV, kBalancedU, kNT),
+            balanced_grid(row_chunks(a.ncols), slots), kThreads, s, FA_WIN(a));
+  return launch_check();
+}
+
+// fa_reduce_f16: VMAX bounds the instantiations (the sums' registers per oct, fa_geometry.hpp)
+template <class HP, int DIV, int VMAX>
+int launch_reduce_h16(const uint16_t* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
+                      const EpiH16& e, hipStream_t s) {
+  const Plan p = plan_f16_window(VMAX, ncols, device_cus());
+  const typename HP::w_t* wt = static_cast<const typename HP::w_t*>(w);
+#define FA_ROWS_H16(V, DEPTH, W)                                                                               \
+  case V * 100 + W:                                                                                            \
+    if constexpr (V <= VMAX) {                                                                                 \
+      if (p.D != DEPTH) break;                                                                                 \
+      FA_LAUNCH_AS(HInst, reduce_kernel_rows_h16, (HP, DIV, V, DEPTH, W, kNT), p.grid, 64 * W, s, stack,       \
+                   stride, n, wt, col0, ncols, e);                                                             \
+      return launch_check();                                                                                   \
+    }                                                                                                          \
+    break
+  switch (p.V * 100 + p.W) {
+    FA_ROWS_H16(1, 16, 1);
+    FA_ROWS_H16(1, 16, 4);
+    FA_ROWS_H16(2, 8, 4);
+    FA_ROWS_H16(4, 4, 4);
+    FA_ROWS_H16(8, 2, 4);
+    FA_ROWS_H16(16, 1, 4);
+  }
+#undef FA_ROWS_H16
+  return no_kernel("reduce_kernel_rows_h16");
 }
 
 // Segmented row-pointer reduce (fa_reduce_f32_rows): reduce_kernel_segrows_rm — blocks claim
@@ -438,31 +345,6 @@ int launch_segrows(const float* const* rows, int n, const void* w, const fa_piec
   constexpr bool XLS = sizeof(T) == 8 && OP != FA_OP_MEAN;
   FA_LAUNCH(reduce_kernel_segrows_rm, (P, T, OP, kSegV, kSegW, KG, 16, kNT, false, XLS), grid, 64 * kSegW, s, rows, n,
             wt, pieces, npieces, work, e);
-  return launch_check();
-}
-
-// Split-N geometry (tools/tune_splitn.py, profiles/r02/tune_splitn): one 1-KiB chunk of every row
-// per block, kSplitW client splits (one per wave), each a rolling pipeline kSplitD rows deep.
-// 1000 x 44,416 fp32: 28.7 us vs 50.2 us sequential; 4000 x 44,416: 111 vs 184 us; but
-// 1000 x 1 M (3907 chunks): 738 vs 572 us — so the split form is used only for windows of fewer
-// 1-KiB chunks than CUs, and with at least 2 * kSplitW clients.  And at most kSplitMaxN clients:
-// a reordered fp32 sum differs from the sequential one by about the sequential sum's own rounding
-// error, which grows like sqrt(N), and the contract is <= 1e-6 per tensor.  The exact CPU
-// restatement of both orders (tests/splitn_error.py, profiles/r03/splitn_error.json; LeNet5
-// tensors, 3 seeds x 3 weight kinds x 2 data kinds) puts the worst tensor at 6.2e-7 for N = 256,
-// 7.4e-7 at 512, 2.5e-6 at 1024 (a 6-element bias, MOON weights), 1.3e-6 at 2048 — so 256.
-// Columns whose terms nearly cancel are re-summed in order by the kernel's guard.
-constexpr int kSplitW = 4, kSplitD = 8, kSplitMaxN = 256;
-constexpr int kSplitS = kSplitW;
-
-template <class P, int OP, typename T>
-int launch_splitn(const float* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
-                  const Epi<T>& e, hipStream_t s) {
-  const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
-  if (n < 2 * kSplitS || n > kSplitMaxN || chunks >= device_cus())  // see kSplitMaxN
-    return launch_reduce<P, OP>(stack, stride, n, w, col0, ncols, e, s);
-  FA_LAUNCH(reduce_kernel_splitn, (P, T, OP, kSplitW, kSplitD, kNT), chunks, 64 * kSplitW, s, stack, stride, n,
-            static_cast<const typename P::w_t*>(w), col0, ncols, e);
   return launch_check();
 }
 
@@ -545,62 +427,87 @@ int check_columns(const float* out32, const double* out64, const void* prev, con
   return FA_OK;
 }
 
-template <typename X>
-int check_common(const X* stack, int64_t stride, int n, const void* w, int64_t col0,
-                 int64_t ncols, const void* o1, const void* o2) {
+// What every fa_reduce_* entry checks first, in this order
+int check_window(const void* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
+                 bool has_output) {
   if (n <= 0) return fail(FA_ERR_ARG, "n_clients must be >= 1");
   if (ncols < 0 || col0 < 0 || stride < col0 + ncols) return fail(FA_ERR_ARG, "bad column window");
   if (!stack || !w) return fail(FA_ERR_ARG, "null stack or weights");
-  if (!o1 && !o2) return fail(FA_ERR_ARG, "no output");
+  if (!has_output) return fail(FA_ERR_ARG, "no output");
+  return FA_OK;
+}
+
+template <typename X>
+int check_common(const X* stack, int64_t stride, int n, const void* w, int64_t col0,
+                 int64_t ncols, const void* o1, const void* o2) {
+  if (int rc = check_window(stack, stride, n, w, col0, ncols, o1 || o2)) return rc;
   if (!aligned_window(stack, stride, col0)) return fail(FA_ERR_ALIGN, "row window not 16-B aligned");
   return FA_OK;
 }
 
-// float16 client stacks (fa_reduce_f16): the geometry of launch_reduce_window's one-piece-per-block
-// branch for an fp32 window of the same BYTE width — ~0.75 blocks per CU (up to one per CU instead
-// of a nearly empty second round), 4 waves, the narrowest piece (V KiB per wave) that covers the
-// block's share, D = 64/(V*W) rows deep (~64 KiB of client rows in flight per block).  Wider
-// windows are swept piece after piece (column-major).  Vmax follows the sums' registers per oct:
-// 4 VGPRs (f16 sums) 16, 8 (fp32 sums) 8, 16 (f64 sums) 4.  A window of at most one chunk per
-// block runs as single-wave blocks, 16 rows deep.
-template <class HP, int DIV, int V, int W>
-int launch_rows_h16(const uint16_t* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
-                    const EpiH16& e, int64_t grid, hipStream_t s) {
-  constexpr int D = V * W >= kPieceChunks ? 1 : (kPieceChunks / (V * W) > 16 ? 16 : kPieceChunks / (V * W));
-  hipLaunchKernelGGL((reduce_kernel_rows_h16<HP, DIV, V, D, W, kNT>), dim3((unsigned)grid), dim3(64 * W), 0, s, stack,
-                     stride, n, static_cast<const typename HP::w_t*>(w), col0, ncols, e);
-  static const std::string name =
-      make_kernel_name("reduce_kernel_rows_h16", pretty_of<HInst<HP, DIV, V, D, W, kNT>>());
-  note_launch(name, grid);
-  return launch_check();
+// fa_reduce_f32 and fa_reduce_f32_splitn (reorder: the caller allows the split-N order)
+int reduce_f32(bool reorder, const float* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
+               const void* weights, double denom, int64_t col_begin, int64_t n_cols, const fa_epilogue* epi,
+               float* out32, double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
+  int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out32, out64);
+  if (rc) return rc;
+  if (n_cols == 0) return FA_OK;
+  const int op = epi ? epi->op : FA_OP_MEAN;
+  if ((rc = check_columns(out32, out64, epi ? epi->prev : nullptr, epi ? epi->v : nullptr,
+                          mode == FA_MODE_W32_DIV32 ? sizeof(float) : sizeof(double),
+                          epi ? epi->h : nullptr)))
+    return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_mode(mode, epi, denom, n_clients, out32, out64, n_cols, [&](auto p, const auto& e) {
+    return with_op(op, [&](auto OP) {
+      return launch_reduce<decltype(p), OP()>(mode, reorder, stack, row_stride, n_clients, weights, col_begin, n_cols,
+                                              e, s);
+    });
+  });
 }
 
-template <class HP, int DIV, int VMAX>
-int launch_reduce_h16(const uint16_t* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
-                      const EpiH16& e, hipStream_t s) {
-  constexpr int W = 4;
-  const int cus = device_cus();
-  const int64_t chunks = ((ncols + 7) / 8 + 63) / 64;  // 1-KiB row pieces
-  int64_t grid = (int64_t)(cus * kRowsBlocksPerCU + 0.5);
-  if (chunks > grid * kPieceChunks && chunks <= (int64_t)cus * kPieceChunks)
-    grid = (chunks + kPieceChunks - 1) / kPieceChunks;
-  if (grid < 1) grid = 1;
-  if (grid > chunks) grid = chunks;
-  const int64_t share = (chunks + grid - 1) / grid;  // chunks per block
-  if (share <= 1) return launch_rows_h16<HP, DIV, 1, 1>(stack, stride, n, w, col0, ncols, e, grid, s);
-  if (share <= 1 * W) return launch_rows_h16<HP, DIV, 1, W>(stack, stride, n, w, col0, ncols, e, grid, s);
-  if (share <= 2 * W || VMAX <= 2) return launch_rows_h16<HP, DIV, 2, W>(stack, stride, n, w, col0, ncols, e, grid, s);
-  if (share <= 4 * W || VMAX <= 4) return launch_rows_h16<HP, DIV, 4, W>(stack, stride, n, w, col0, ncols, e, grid, s);
-  if constexpr (VMAX >= 8) {
-    if (share <= 8 * W || VMAX <= 8) return launch_rows_h16<HP, DIV, 8, W>(stack, stride, n, w, col0, ncols, e, grid, s);
+// fa_reduce_f64 (P = AccF64) and fa_reduce_i64 (AccI64)
+template <class P>
+int reduce_8byte(const typename P::x_t* stack, int64_t row_stride, int32_t n_clients,
+                 const typename P::w_t* weights, double denom, int64_t col_begin, int64_t n_cols, double* out64,
+                 void* stream) {
+  g_last_launch = LaunchRecord{};
+  int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out64, nullptr);
+  if (rc) return rc;
+  if (n_cols == 0) return FA_OK;
+  if ((rc = check_columns(nullptr, out64, nullptr, nullptr, 8))) return rc;
+  Window<P, double> a{stack, row_stride, n_clients, weights, col_begin, n_cols, {}};
+  make_epi<double>(nullptr, denom, n_clients, nullptr, out64, &a.e);
+  return launch_balanced(a, static_cast<hipStream_t>(stream));
+}
+
+// fa_gather_rows*: the shared argument checks (`bad`: the entry's own complaint, checked after
+// them), then one launch(grid, i0) per tile of up to 65535 clients (the grid's y limit)
+template <class F>
+int gather_tiles(const void* stack, int64_t row_stride, int32_t n_clients, const void* rows, const int64_t* segs,
+                 int32_t n_segments, const char* bad, F&& launch) {
+  if (n_clients < 0 || n_segments < 0 || row_stride < 0) return fail(FA_ERR_ARG, "bad gather sizes");
+  if (n_clients == 0 || n_segments == 0) return FA_OK;
+  if (!stack || !rows || !segs) return fail(FA_ERR_ARG, "null gather pointer");
+  if (bad) return fail(FA_ERR_ARG, bad);
+  for (int32_t i0 = 0; i0 < n_clients; i0 += 65535) {
+    launch(dim3((unsigned)n_segments, (unsigned)std::min<int32_t>(65535, n_clients - i0)), i0);
+    if (int rc = launch_check()) return rc;
   }
-  if constexpr (VMAX >= 16) return launch_rows_h16<HP, DIV, 16, W>(stack, stride, n, w, col0, ncols, e, grid, s);
-  return fail(FA_ERR_ARG, "no float16 geometry");  // not reached
+  return FA_OK;
 }
 
-}  // namespace
+template <typename E>
+int gather_rows(void* stack, int64_t row_stride, int32_t n_clients, const void* const* rows, const int64_t* segs,
+                int32_t n_segments, void* stream, const char* bad = nullptr) {
+  return gather_tiles(stack, row_stride, n_clients, rows, segs, n_segments, bad, [&](dim3 grid, int32_t i0) {
+    hipLaunchKernelGGL(gather_rows_kernel<E>, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<E*>(stack), row_stride, n_clients, reinterpret_cast<const E* const*>(rows), segs,
+                       n_segments, i0);
+  });
+}
 
-namespace {
 // Piece cut of one segment: `pc` chunks at most, equal pieces (the last one takes the remainder)
 template <typename F>
 void cut_segment(int64_t len, int64_t pc, F&& emit) {
@@ -621,78 +528,35 @@ const char* fa_last_error(void) { return g_last_error.c_str(); }
 int fa_reduce_f32(const float* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
                   const void* weights, double denom, int64_t col_begin, int64_t n_cols,
                   const fa_epilogue* epi, float* out32, double* out64, void* stream) {
-  g_last_launch = LaunchRecord{};
-  int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out32, out64);
-  if (rc) return rc;
-  if (n_cols == 0) return FA_OK;
-  const int op = epi ? epi->op : FA_OP_MEAN;
-  if ((rc = check_columns(out32, out64, epi ? epi->prev : nullptr, epi ? epi->v : nullptr,
-                          mode == FA_MODE_W32_DIV32 ? sizeof(float) : sizeof(double),
-                          epi ? epi->h : nullptr)))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return with_mode(mode, epi, denom, n_clients, out32, out64, n_cols, [&](auto p, const auto& e) {
-    return with_op(op, [&](auto OP) {
-      return launch_reduce<decltype(p), OP()>(stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
-    });
-  });
+  return reduce_f32(false, stack, row_stride, n_clients, mode, weights, denom, col_begin, n_cols, epi, out32, out64,
+                    stream);
 }
 
 int fa_reduce_f32_splitn(const float* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
                          const void* weights, double denom, int64_t col_begin, int64_t n_cols,
                          const fa_epilogue* epi, float* out32, double* out64, void* stream) {
-  g_last_launch = LaunchRecord{};
-  int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out32, out64);
-  if (rc) return rc;
-  if (n_cols == 0) return FA_OK;
-  const int op = epi ? epi->op : FA_OP_MEAN;
-  if ((rc = check_columns(out32, out64, epi ? epi->prev : nullptr, epi ? epi->v : nullptr,
-                          mode == FA_MODE_W32_DIV32 ? sizeof(float) : sizeof(double), epi ? epi->h : nullptr)))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return with_mode(mode, epi, denom, n_clients, out32, out64, n_cols, [&](auto p, const auto& e) {
-    return with_op(op, [&](auto OP) {
-      return launch_splitn<decltype(p), OP()>(stack, row_stride, n_clients, weights, col_begin, n_cols, e, s);
-    });
-  });
+  return reduce_f32(true, stack, row_stride, n_clients, mode, weights, denom, col_begin, n_cols, epi, out32, out64,
+                    stream);
 }
 
 int fa_reduce_f64(const double* stack, int64_t row_stride, int32_t n_clients,
                   const double* weights, double denom, int64_t col_begin, int64_t n_cols,
                   double* out64, void* stream) {
-  g_last_launch = LaunchRecord{};
-  int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out64, nullptr);
-  if (rc) return rc;
-  if (n_cols == 0) return FA_OK;
-  if ((rc = check_columns(nullptr, out64, nullptr, nullptr, 8))) return rc;
-  Epi<double> e;
-  make_epi<double>(nullptr, denom, n_clients, nullptr, out64, &e);
-  return launch_reduce<AccF64, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
-                                                   n_cols, e, static_cast<hipStream_t>(stream));
+  return reduce_8byte<AccF64>(stack, row_stride, n_clients, weights, denom, col_begin, n_cols, out64, stream);
 }
 
 int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
                   const int64_t* weights, double denom, int64_t col_begin, int64_t n_cols,
                   double* out64, void* stream) {
-  g_last_launch = LaunchRecord{};
-  int rc = check_common(stack, row_stride, n_clients, weights, col_begin, n_cols, out64, nullptr);
-  if (rc) return rc;
-  if (n_cols == 0) return FA_OK;
-  if ((rc = check_columns(nullptr, out64, nullptr, nullptr, 8))) return rc;
-  Epi<double> e;
-  make_epi<double>(nullptr, denom, n_clients, nullptr, out64, &e);
-  return launch_reduce<AccI64, FA_OP_MEAN>(stack, row_stride, n_clients, weights, col_begin,
-                                                   n_cols, e, static_cast<hipStream_t>(stream));
+  return reduce_8byte<AccI64>(stack, row_stride, n_clients, weights, denom, col_begin, n_cols, out64, stream);
 }
 
 int fa_reduce_f16(const void* stack, int64_t row_stride, int32_t n_clients, int32_t mode, const void* weights,
                   double denom, int64_t col_begin, int64_t n_cols, void* out16, float* out32, double* out64,
                   void* stream) {
   g_last_launch = LaunchRecord{};
-  if (n_clients <= 0) return fail(FA_ERR_ARG, "n_clients must be >= 1");
-  if (n_cols < 0 || col_begin < 0 || row_stride < col_begin + n_cols) return fail(FA_ERR_ARG, "bad column window");
-  if (!stack || !weights) return fail(FA_ERR_ARG, "null stack or weights");
-  if (!out16 && !out32 && !out64) return fail(FA_ERR_ARG, "no output");
+  if (int rc = check_window(stack, row_stride, n_clients, weights, col_begin, n_cols, out16 || out32 || out64))
+    return rc;
   if (mode < FA_MODE_H16_NUMPY || mode > FA_MODE_H16_W64) return fail(FA_ERR_ARG, "unknown float16 reduce mode");
   if (!aligned_to(stack, 16) || row_stride % 8 != 0 || col_begin % 8 != 0)
     return fail(FA_ERR_ALIGN, "float16 row window not 16-B aligned (stack, row_stride and col_begin in units of 8)");
@@ -843,58 +707,29 @@ int fa_reduce_f32_rows(const float* const* rows, int32_t n_clients, int32_t mode
 
 int fa_gather_rows(void* stack, int64_t row_stride, int32_t n_clients, int32_t elem_size,
                    const void* const* rows, const int64_t* segs, int32_t n_segments, void* stream) {
-  if (n_clients < 0 || n_segments < 0 || row_stride < 0) return fail(FA_ERR_ARG, "bad gather sizes");
-  if (n_clients == 0 || n_segments == 0) return FA_OK;
-  if (!stack || !rows || !segs) return fail(FA_ERR_ARG, "null gather pointer");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (elem_size != 4 && elem_size != 8) return fail(FA_ERR_ARG, "elem_size must be 4 or 8");
-  // one launch per tile of up to 65535 clients (the grid's y limit)
-  for (int32_t i0 = 0; i0 < n_clients; i0 += 65535) {
-    const dim3 grid((unsigned)n_segments, (unsigned)std::min<int32_t>(65535, n_clients - i0));
-    if (elem_size == 4)
-      hipLaunchKernelGGL(gather_rows_kernel<uint32_t>, grid, dim3(kThreads), 0, s, static_cast<uint32_t*>(stack),
-                         row_stride, n_clients, reinterpret_cast<const uint32_t* const*>(rows), segs, n_segments, i0);
-    else
-      hipLaunchKernelGGL(gather_rows_kernel<uint64_t>, grid, dim3(kThreads), 0, s, static_cast<uint64_t*>(stack),
-                         row_stride, n_clients, reinterpret_cast<const uint64_t* const*>(rows), segs, n_segments, i0);
-    if (int rc = launch_check()) return rc;
-  }
-  return FA_OK;
+  const char* bad = elem_size != 4 && elem_size != 8 ? "elem_size must be 4 or 8" : nullptr;
+  if (elem_size == 8) return gather_rows<uint64_t>(stack, row_stride, n_clients, rows, segs, n_segments, stream, bad);
+  return gather_rows<uint32_t>(stack, row_stride, n_clients, rows, segs, n_segments, stream, bad);
 }
 
 int fa_gather_rows_f16(void* stack, int64_t row_stride, int32_t n_clients, const void* const* rows,
                        const int64_t* segs, int32_t n_segments, void* stream) {
-  if (n_clients < 0 || n_segments < 0 || row_stride < 0) return fail(FA_ERR_ARG, "bad gather sizes");
-  if (n_clients == 0 || n_segments == 0) return FA_OK;
-  if (!stack || !rows || !segs) return fail(FA_ERR_ARG, "null gather pointer");
-  for (int32_t i0 = 0; i0 < n_clients; i0 += 65535) {
-    hipLaunchKernelGGL(gather_rows_kernel<uint16_t>,
-                       dim3((unsigned)n_segments, (unsigned)std::min<int32_t>(65535, n_clients - i0)), dim3(kThreads), 0,
-                       static_cast<hipStream_t>(stream), static_cast<uint16_t*>(stack), row_stride, n_clients,
-                       reinterpret_cast<const uint16_t* const*>(rows), segs, n_segments, i0);
-    if (int rc = launch_check()) return rc;
-  }
-  return FA_OK;
+  return gather_rows<uint16_t>(stack, row_stride, n_clients, rows, segs, n_segments, stream);
 }
 
 int fa_gather_rows_f64(double* stack, int64_t row_stride, int32_t n_clients, const void* const* rows,
                        const int64_t* segs, int32_t n_segments, void* stream) {
-  if (n_clients < 0 || n_segments < 0 || row_stride < 0) return fail(FA_ERR_ARG, "bad gather sizes");
-  if (n_clients == 0 || n_segments == 0) return FA_OK;
-  if (!stack || !rows || !segs) return fail(FA_ERR_ARG, "null gather pointer");
-  for (int32_t i0 = 0; i0 < n_clients; i0 += 65535) {
-    hipLaunchKernelGGL(gather_rows_f64_kernel, dim3((unsigned)n_segments, (unsigned)std::min<int32_t>(65535, n_clients - i0)),
-                       dim3(kThreads), 0, static_cast<hipStream_t>(stream), stack, row_stride, n_clients, rows, segs,
-                       n_segments, i0);
-    if (int rc = launch_check()) return rc;
-  }
-  return FA_OK;
+  return gather_tiles(stack, row_stride, n_clients, rows, segs, n_segments, nullptr, [&](dim3 grid, int32_t i0) {
+    hipLaunchKernelGGL(gather_rows_f64_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), stack,
+                       row_stride, n_clients, rows, segs, n_segments, i0);
+  });
 }
 
 int fa_reduce_windows(int32_t op, int64_t n_cols) {
   if (n_cols < 0) return fail(FA_ERR_ARG, "negative n_cols");
   if (g_reduce_grid.load(std::memory_order_relaxed) > 0) return 1;
-  return with_op(op, [&](auto OP) { return window_count<OP()>(n_cols); });
+  if (op < FA_OP_MEAN || op > FA_OP_DYN) return fail(FA_ERR_ARG, "unknown epilogue op");
+  return window_count(op, n_cols);
 }
 
 int fa_set_reduce_grid(int32_t grid) {

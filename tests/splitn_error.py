@@ -3,7 +3,7 @@ sum, per fp32 tensor, as a function of the client count — computed exactly on 
 oracle's restatement of both orders (oracle.c_reduce vs oracle.c_reduce_splitn, which the GPU
 tests pin bit for bit to the kernels); --guard applies the kernel's cancellation guard (columns
 whose terms nearly cancel take the sequential sum).  Drives the split-N selection limit (kSplitMaxN in
-flearn_amd/csrc/fa_reduce.hip).  Test infrastructure / measurement only.
+flearn_amd/csrc/fa_geometry.hpp).  Test infrastructure / measurement only.
 
     python tests/splitn_error.py [--out profiles/r03/splitn_error.json]
 """

@@ -507,7 +507,7 @@ def _oracle_columns(n, c0, width, seed, op, prev_h):
 
 
 def _rowmajor_piece_starts(p, cus=256):
-    """Column starts of the row-major kernel's pieces and KG groups (mirror of fa_reduce.hip
+    """Column starts of the row-major kernel's pieces and KG groups (mirror of fa_geometry.hpp
     rowmajor_geometry + reduce_kernel_rowmajor's split), for placing check windows on them."""
     chunks = ((p + 3) // 4 + 63) // 64
     for d in range(0, cus - 160 + 1):

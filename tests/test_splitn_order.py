@@ -15,11 +15,11 @@ from flearn_amd import layouts
 from splitn_error import data, tensors, weights
 
 TOL = 1e-6
-HIP = Path(__file__).resolve().parent.parent / "flearn_amd" / "csrc" / "fa_reduce.hip"
+GEOMETRY = Path(__file__).resolve().parent.parent / "flearn_amd" / "csrc" / "fa_geometry.hpp"
 
 
 def split_max_n():
-    m = re.search(r"kSplitMaxN\s*=\s*(\d+)", HIP.read_text())
+    m = re.search(r"kSplitMaxN\s*=\s*(\d+)", GEOMETRY.read_text())
     return int(m.group(1))
 
 

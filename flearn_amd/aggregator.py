@@ -17,13 +17,17 @@ tensors directly and are what bench.py and the multi-GPU path use.
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _native as na
-from .bucket import BucketPlan, Packer, RowTable, make_plan
+from .bucket import (FMT, SMALL_BYTES, TORCH_DTYPE, AsyncPack, BucketPlan, NativeRows, Packer, RowTable, Shard,
+                     make_plan, rank_width)
+from .dist import DoubleBuffer, gather_columns
 from .semantics import KIND_F16, KIND_F32, KIND_F64, KIND_I64, Numerics
+from .wire import wire_row
 
 _F64 = np.dtype(np.float64)
 _ONE_W32 = Numerics(KIND_F32, na.MODE_W32_DIV64, np.ones(1, np.float32), 1.0, np.dtype(np.float32), _F64)  # fl32(1.0)
@@ -42,6 +46,41 @@ def _check_cuda(t: torch.Tensor, name: str, dtype: torch.dtype, ndim: int | None
         raise ValueError(f"{name} must be {ndim}-D, got shape {tuple(t.shape)}")
 
 
+def _check_window(shape, col_begin, n_cols, n_clients):
+    """(n, ncols) of the window [col_begin, +n_cols) over the first n_clients rows of a stack."""
+    n = shape[0] if n_clients is None else n_clients
+    if not 1 <= n <= shape[0]:
+        raise ValueError("n_clients out of range")
+    ncols = shape[1] - col_begin if n_cols is None else n_cols
+    if col_begin < 0 or ncols < 0 or col_begin + ncols > shape[1]:
+        raise ValueError("column window out of range")
+    return n, ncols
+
+
+def _check_stack(stack, dtype, col_begin, n_cols, n_clients):
+    _check_cuda(stack, "stack", dtype, 2)
+    if stack.stride(1) != 1:
+        raise ValueError("stack rows must be contiguous")
+    return _check_window(stack.shape, col_begin, n_cols, n_clients)
+
+
+def _check_weights(weights, dtype, n):
+    _check_cuda(weights, "weights", dtype)
+    if weights.numel() < n:
+        raise ValueError("fewer weights than clients")
+
+
+def _check_arrays(ncols, *arrays, optional=True):
+    """Every (name, tensor, dtype) the launch reads or writes ncols elements of: CUDA, dtype,
+    contiguous, long enough.  optional: None is allowed (that output is not wanted)."""
+    for name, t, dt in arrays:
+        if t is None and optional:
+            continue
+        _check_cuda(t, name, dt)
+        if t.numel() < ncols or not t.is_contiguous():
+            raise ValueError(f"{name} too small or not contiguous")
+
+
 def _epilogue(op: int, prev, v, beta=0.9, eta=1e-1, tau=1e-9, beta2=0.99, h=None, alpha=0.0, n_dyn=0, v_out=None):
     return na.Epilogue(op, 0, _ptr(prev), _ptr(v), beta, eta, tau, beta2, _ptr(h), alpha, float(n_dyn), _ptr(v_out))
 
@@ -55,9 +94,7 @@ def _check_v_out(v_out, v, ncols, others=()):
     the epilogue reads (prev, h): the kernel's stores would race its loads."""
     if v_out is None:
         return
-    _check_cuda(v_out, "v_out", v.dtype)
-    if v_out.numel() < ncols or not v_out.is_contiguous():
-        raise ValueError("v_out too small or not contiguous")
+    _check_arrays(ncols, ("v_out", v_out, v.dtype))
     if v_out.data_ptr() == v.data_ptr():
         raise ValueError("v_out must be None (in place) or another buffer")
     o0, o1 = _byte_range(v_out, ncols)
@@ -116,40 +153,19 @@ def reduce_stack(
             raise ValueError("a row table is reduced over its whole bucket")
         if n_clients is not None and n_clients != stack.shape[0]:
             raise ValueError("a row table is reduced over all of its clients")
+        n, ncols = _check_window(stack.shape, col_begin, n_cols, n_clients)
     else:
-        _check_cuda(stack, "stack", torch.float32, 2)
-        if stack.stride(1) != 1:
-            raise ValueError("stack rows must be contiguous")
-    n = stack.shape[0] if n_clients is None else n_clients
-    if not 1 <= n <= stack.shape[0]:
-        raise ValueError("n_clients out of range")
-    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
-    if col_begin < 0 or ncols < 0 or col_begin + ncols > stack.shape[1]:
-        raise ValueError("column window out of range")
-    wdt = torch.float64 if mode == na.MODE_W64 else torch.float32
-    _check_cuda(weights, "weights", wdt)
-    if weights.numel() < n:
-        raise ValueError("fewer weights than clients")
-    for name, t, dt in (("out32", out32, torch.float32), ("out64", out64, torch.float64)):
-        if t is not None:
-            _check_cuda(t, name, dt)
-            if t.numel() < ncols or not t.is_contiguous():
-                raise ValueError(f"{name} too small or not contiguous")
+        n, ncols = _check_stack(stack, torch.float32, col_begin, n_cols, n_clients)
+    _check_weights(weights, torch.float64 if mode == na.MODE_W64 else torch.float32, n)
+    _check_arrays(ncols, ("out32", out32, torch.float32), ("out64", out64, torch.float64))
+    vdt = torch.float32 if mode == na.MODE_W32_DIV32 else torch.float64
     epi = None
     if op == na.OP_DYN:
-        vdt = torch.float32 if mode == na.MODE_W32_DIV32 else torch.float64
-        _check_cuda(h, "h", torch.float32)
-        _check_cuda(v, "theta", vdt)
-        if h.numel() < ncols or v.numel() < ncols:
-            raise ValueError("h / theta too small")
+        _check_arrays(ncols, ("h", h, torch.float32), ("theta", v, vdt), optional=False)
         _check_v_out(v_out, v, ncols, (("h", h),))
         epi = _epilogue(op, None, v, h=h, alpha=alpha, n_dyn=n, v_out=v_out)
     elif op != na.OP_MEAN:
-        vdt = torch.float32 if mode == na.MODE_W32_DIV32 else torch.float64
-        _check_cuda(prev, "prev", torch.float32)
-        _check_cuda(v, "v", vdt)
-        if prev.numel() < ncols or v.numel() < ncols:
-            raise ValueError("prev / v too small")
+        _check_arrays(ncols, ("prev", prev, torch.float32), ("v", v, vdt), optional=False)
         _check_v_out(v_out, v, ncols, (("prev", prev),))
         epi = _epilogue(op, prev, v, beta, eta, tau, beta2, v_out=v_out)
     if rows:
@@ -172,27 +188,26 @@ def reduce_stack(
     na.check(rc, "fa_reduce_f32_splitn" if reorder else "fa_reduce_f32")
 
 
-def _window(stack, col_begin, n_cols, out64):
-    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
-    if col_begin < 0 or ncols < 0 or col_begin + ncols > stack.shape[1]:
-        raise ValueError("column window out of range")
-    if out64.numel() < ncols or not out64.is_contiguous():
-        raise ValueError("out64 too small or not contiguous")
-    return ncols
+def _reduce_stack8(dtype, entry, stack, weights, denom, out64, n_clients, col_begin, n_cols):
+    """The 8-byte kernels' shared body: entry = fa_reduce_f64 / fa_reduce_i64, stack and weights in dtype."""
+    n, ncols = _check_stack(stack, dtype, col_begin, n_cols, n_clients)
+    _check_weights(weights, dtype, n)
+    _check_arrays(ncols, ("out64", out64, torch.float64), optional=False)
+    rc = getattr(na.lib(), entry)(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), col_begin,
+                                  ncols, out64.data_ptr(), na.stream_handle(stack.device))
+    na.check(rc, entry)
 
 
 def reduce_stack_f64(stack, weights, denom, out64, n_clients=None, *, col_begin=0, n_cols=None):
     """Weighted mean of the float64 client stack over columns [col_begin, +n_cols) (default: all);
     out64 is indexed from col_begin."""
-    L = na.lib()
-    _check_cuda(stack, "stack", torch.float64, 2)
-    _check_cuda(weights, "weights", torch.float64)
-    _check_cuda(out64, "out64", torch.float64)
-    n = stack.shape[0] if n_clients is None else n_clients
-    ncols = _window(stack, col_begin, n_cols, out64)
-    rc = L.fa_reduce_f64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), col_begin,
-                         ncols, out64.data_ptr(), na.stream_handle(stack.device))
-    na.check(rc, "fa_reduce_f64")
+    _reduce_stack8(torch.float64, "fa_reduce_f64", stack, weights, denom, out64, n_clients, col_begin, n_cols)
+
+
+def reduce_stack_i64(stack, weights, denom, out64, n_clients=None, *, col_begin=0, n_cols=None):
+    """Wrapping int64 weighted sum of the int64 client stack over columns [col_begin, +n_cols)
+    (default: all), then the float64 divide; out64 is indexed from col_begin."""
+    _reduce_stack8(torch.int64, "fa_reduce_i64", stack, weights, denom, out64, n_clients, col_begin, n_cols)
 
 
 def reduce_stack_f16(stack, weights, mode, denom, *, out16=None, out32=None, out64=None, col_begin=0, n_cols=None,
@@ -204,40 +219,13 @@ def reduce_stack_f16(stack, weights, mode, denom, *, out16=None, out32=None, out
     the result in the dtype it is born in, widened exactly, or narrowed through float32 — out16 of a
     float64 result is fl16(fl32(q)), what load_state_dict into a half module stores."""
     L = na.lib()
-    _check_cuda(stack, "stack", torch.float16, 2)
-    if stack.stride(1) != 1:
-        raise ValueError("stack rows must be contiguous")
-    n = stack.shape[0] if n_clients is None else n_clients
-    if not 1 <= n <= stack.shape[0]:
-        raise ValueError("n_clients out of range")
-    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
-    if col_begin < 0 or ncols < 0 or col_begin + ncols > stack.shape[1]:
-        raise ValueError("column window out of range")
-    _check_cuda(weights, "weights", torch.float64 if mode == na.MODE_H16_W64 else torch.float32)
-    if weights.numel() < n:
-        raise ValueError("fewer weights than clients")
-    for name, t, dt in (("out16", out16, torch.float16), ("out32", out32, torch.float32), ("out64", out64, torch.float64)):
-        if t is not None:
-            _check_cuda(t, name, dt)
-            if t.numel() < ncols or not t.is_contiguous():
-                raise ValueError(f"{name} too small or not contiguous")
+    n, ncols = _check_stack(stack, torch.float16, col_begin, n_cols, n_clients)
+    _check_weights(weights, torch.float64 if mode == na.MODE_H16_W64 else torch.float32, n)
+    _check_arrays(ncols, ("out16", out16, torch.float16), ("out32", out32, torch.float32),
+                  ("out64", out64, torch.float64))
     rc = L.fa_reduce_f16(stack.data_ptr(), stack.stride(0), n, mode, weights.data_ptr(), float(denom), col_begin, ncols,
                          _ptr(out16), _ptr(out32), _ptr(out64), na.stream_handle(stack.device))
     na.check(rc, "fa_reduce_f16")
-
-
-def reduce_stack_i64(stack, weights, denom, out64, n_clients=None, *, col_begin=0, n_cols=None):
-    """Wrapping int64 weighted sum of the int64 client stack over columns [col_begin, +n_cols)
-    (default: all), then the float64 divide; out64 is indexed from col_begin."""
-    L = na.lib()
-    _check_cuda(stack, "stack", torch.int64, 2)
-    _check_cuda(weights, "weights", torch.int64)
-    _check_cuda(out64, "out64", torch.float64)
-    n = stack.shape[0] if n_clients is None else n_clients
-    ncols = _window(stack, col_begin, n_cols, out64)
-    rc = L.fa_reduce_i64(stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), float(denom), col_begin,
-                         ncols, out64.data_ptr(), na.stream_handle(stack.device))
-    na.check(rc, "fa_reduce_i64")
 
 
 def apply_update(op: int, local32, glob, v, *, out32=None, out64=None, beta=0.9, eta=1e-1, tau=1e-9,
@@ -251,6 +239,7 @@ def apply_update(op: int, local32, glob, v, *, out32=None, out64=None, beta=0.9,
     n = local32.numel()
     if glob.numel() != n or v.numel() != n:
         raise ValueError("local / glob / v sizes differ")
+    _check_arrays(n, ("v", v, glob.dtype), ("out32", out32, torch.float32), ("out64", out64, torch.float64))
     epi = _epilogue(op, local32, v, beta, eta, tau, beta2)
     rc = L.fa_opt_apply(prec, ctypes.byref(epi), local32.data_ptr(), glob.data_ptr(), n, _ptr(out32),
                         _ptr(out64), na.stream_handle(local32.device))
@@ -268,6 +257,8 @@ def apply_dyn(glob, h, theta, n_clients: int, alpha: float = 0.01, *, out32=None
     n = glob.numel()
     if h.numel() != n or theta.numel() != n:
         raise ValueError("glob / h / theta sizes differ")
+    _check_arrays(n, ("h", h, torch.float32), ("theta", theta, glob.dtype), ("out32", out32, torch.float32),
+                  ("out64", out64, torch.float64))
     epi = _epilogue(na.OP_DYN, None, theta, h=h, alpha=alpha, n_dyn=n_clients)
     rc = L.fa_opt_apply(prec, ctypes.byref(epi), None, glob.data_ptr(), n, _ptr(out32), _ptr(out64),
                         na.stream_handle(glob.device))
@@ -350,6 +341,37 @@ def mean_tables(tables, device=None):
 # ---------------------------------------------------------------------------------------------
 # server-side optimizer state
 # ---------------------------------------------------------------------------------------------
+# ServerOptimizer and DynState keep flat arrays laid out like the f32 bucket, cut into the column
+# shards of the devices (or, with a process group, this rank's columns only).
+
+
+def _layout_signature(plan: BucketPlan, shards):
+    """(segments, shards): what the resident state is bound to between rounds."""
+    return (tuple((s.key, s.shape) for s in plan.f32.segments), tuple((sh.device, sh.c0, sh.c1) for sh in shards))
+
+
+def _flatten(stride: int, dtype, segments, values: dict) -> np.ndarray:
+    """values[key] of every segment at its offset of a zeroed stride-wide host array."""
+    flat = np.zeros(stride, dtype=dtype)
+    for s in segments:
+        flat[s.offset : s.offset + s.numel] = np.asarray(values[s.key], dtype=dtype).reshape(-1)
+    return flat
+
+
+def _to_shards(flat: np.ndarray, shards, dtype=None) -> dict:
+    """shard index -> the shard's columns of the flat host array as a device tensor."""
+    return {sh.index: torch.from_numpy(flat[sh.c0 : sh.c1].copy()).to(sh.device, dtype) for sh in shards}
+
+
+def _bucket_host(cols, stride: int, group) -> np.ndarray:
+    """The per-shard tensors `cols` (in shard order) as one host array over the whole bucket.
+    With a column-sharded process group (group, world) every rank holds only its columns: this is
+    then a collective (an all-gather) that every rank must call."""
+    if group is None:
+        return np.concatenate([t.cpu().numpy() for t in cols])
+    (loc,) = cols
+    pg, world = group
+    return gather_columns(loc, rank_width(stride, world), stride, pg).cpu().numpy()
 
 
 class ServerOptimizer:
@@ -369,8 +391,7 @@ class ServerOptimizer:
         self.op = na.OP_BY_NAME[op]
         self.name = op
         self.beta, self.eta, self.tau, self.beta2 = beta, eta, tau, beta2
-        self.state = {}  # shard index -> (prev, v): the current previous global model and v_t
-        self.spare = {}  # shard index -> (prev, v) buffers the next fused step writes into
+        self.state = {}  # shard index -> (prev, v) DoubleBuffers: the previous global model and v_t
         self._sig = None
         self._pending_init = None
         self._pending_v = None
@@ -411,9 +432,7 @@ class ServerOptimizer:
 
     @staticmethod
     def _signature(plan: BucketPlan, shards):
-        g = plan.f32
-        return (tuple((s.key, s.shape) for s in g.segments), g.numerics.out_dtype.str,
-                tuple((sh.device, sh.c0, sh.c1) for sh in shards))
+        return _layout_signature(plan, shards) + (plan.f32.numerics.out_dtype.str,)
 
     @staticmethod
     def _vdtype(plan):
@@ -425,24 +444,18 @@ class ServerOptimizer:
         g = plan.f32
         sig = self._signature(plan, shards)
         if self._pending_init is not None:
-            prev = np.zeros(g.stride, dtype=np.float32)
+            prev = _flatten(g.stride, np.float32, g.segments, self._pending_init)
             vdt = np.float32 if self._vdtype(plan) == torch.float32 else np.float64
             vflat = np.zeros(g.stride, dtype=vdt)
-            for s in g.segments:
-                prev[s.offset : s.offset + s.numel] = np.asarray(self._pending_init[s.key], np.float32).reshape(-1)
-                if self._pending_v is not None:
+            if self._pending_v is not None:
+                for s in g.segments:
                     if s.key not in self._pending_v:
                         raise KeyError(s.key)
-                    v = np.asarray(self._pending_v[s.key])
+                    v = self._pending_v[s.key]
                     if tuple(v.shape) != tuple(s.shape):
                         raise ValueError(f"v_t[{s.key!r}] shape {v.shape} != model shape {tuple(s.shape)}")
-                    vflat[s.offset : s.offset + s.numel] = v.astype(vdt, copy=False).reshape(-1)
-            self.state = {
-                sh.index: (torch.from_numpy(prev[sh.c0 : sh.c1].copy()).to(sh.device),
-                           torch.from_numpy(vflat[sh.c0 : sh.c1].copy()).to(sh.device))
-                for sh in shards
-            }
-            self._sig, self._plan = sig, plan
+                vflat = _flatten(g.stride, vdt, g.segments, self._pending_v)
+            self._bind(plan, shards, _to_shards(prev, shards), _to_shards(vflat, shards))
             self._pending_init = self._pending_v = None
             return True
         if self._sig is None:
@@ -454,32 +467,30 @@ class ServerOptimizer:
 
     def adopt(self, plan: BucketPlan, shards, means: dict):
         """First round: the fp32 mean becomes prev, v_t = 0.  means: shard index -> fp32 tensor."""
-        self.state = {sh.index: (means[sh.index][: sh.width].clone(),
-                                 torch.zeros(sh.width, dtype=self._vdtype(plan), device=sh.device))
-                      for sh in shards}
+        self._bind(plan, shards, {sh.index: means[sh.index][: sh.width].clone() for sh in shards},
+                   {sh.index: torch.zeros(sh.width, dtype=self._vdtype(plan), device=sh.device) for sh in shards})
+
+    def _bind(self, plan: BucketPlan, shards, prev: dict, v: dict):
+        """New state (fresh double buffers) bound to this plan and these shards."""
+        self.state = {sh.index: (DoubleBuffer(prev[sh.index]), DoubleBuffer(v[sh.index])) for sh in shards}
         self._sig, self._plan = self._signature(plan, shards), plan
 
-    def swap_buffers(self, sh):
-        """(prev, v, prev_out, v_out) of a fused step on shard sh, and the state advanced to the
-        output pair: the step reads the current pair and writes the other one (double-buffered,
-        DESIGN.md §4 finding 20); the pair it read becomes the next step's output."""
+    def step_buffers(self, sh):
+        """(prev, v, prev_out, v_out) of a fused step on shard sh: it reads the current pair and
+        writes the other one (double-buffered, DESIGN.md §4 finding 20).  `advance(sh)` makes the
+        output pair the state — once the launch call has returned, never before."""
         prev, v = self.state[sh.index]
-        spare = self.spare.get(sh.index)
-        if spare is None or spare[0].shape != prev.shape or spare[1].dtype != v.dtype or spare[0].device != prev.device:
-            spare = (torch.empty_like(prev), torch.empty_like(v))
-        self.state[sh.index], self.spare[sh.index] = spare, (prev, v)
-        return prev, v, spare[0], spare[1]
+        return prev.cur, v.cur, prev.other, v.other
 
-    def unswap(self, sh):
-        """Undo swap_buffers(sh) when the fused step it was for did not run (the state keeps the
-        pair it had: the spare buffers hold nothing yet)."""
-        self.state[sh.index], self.spare[sh.index] = self.spare[sh.index], self.state[sh.index]
+    def advance(self, sh):
+        prev, v = self.state[sh.index]
+        prev.flip()
+        v.flip()
 
     def v_t(self, plan: BucketPlan | None = None) -> dict:
         """The state as the reference exposes it (self.v_t dict of arrays; plan: the last round's by
-        default).  With a column-sharded
-        process group (Aggregator(group=...)) every rank holds only its columns: this is then a
-        collective (an all-gather) that every rank must call."""
+        default).  With a column-sharded process group (Aggregator(group=...)) every rank holds
+        only its columns: this is then a collective (an all-gather) that every rank must call."""
         return self._host_dict(plan, 1)
 
     def _host_dict(self, plan: BucketPlan, i: int) -> dict:
@@ -487,16 +498,7 @@ class ServerOptimizer:
         plan = plan if plan is not None else self._plan
         if not self.state or plan is None:
             raise RuntimeError("no server optimizer state yet (no fused round has run)")
-        if self.group is not None:
-            from .bucket import rank_width
-            from .dist import gather_columns
-
-            (loc,) = [self.state[j][i] for j in sorted(self.state)]
-            group, world = self.group
-            stride = plan.f32.stride
-            host = gather_columns(loc, rank_width(stride, world), stride, group).cpu().numpy()
-        else:
-            host = np.concatenate([self.state[j][i].cpu().numpy() for j in sorted(self.state)])
+        host = _bucket_host([self.state[j][i].cur for j in sorted(self.state)], plan.f32.stride, self.group)
         return {s.key: host[s.offset : s.offset + s.numel].reshape(s.shape).copy() for s in plan.f32.segments}
 
 
@@ -532,8 +534,8 @@ class DynState:
         self.alpha = alpha
         self.h_host = h
         self._theta_init = None if h is None else {k: np.array(_as_host(v), copy=True) for k, v in h.items()}
-        self.state = {}  # shard index -> (h fp32, theta)
-        self._spare = {}  # shard index -> the theta buffer the next fused round writes into
+        self.state = {}  # shard index -> (h fp32, theta DoubleBuffer)
+        self._plan = None  # the bucket plan the state is bound to (the last round's)
         self._sig = None
         self._tdt = None
         self._dirty = False
@@ -582,21 +584,12 @@ class DynState:
         g = plan.f32
         dev, skip = self.classify(plan)
         tdt = torch.float32 if g.numerics.out_dtype == np.float32 else torch.float64
-        sig = (tuple((s.key, s.shape) for s in g.segments), tuple(dev),
-               tuple((sh.device, sh.c0, sh.c1) for sh in shards))
+        sig = _layout_signature(plan, shards) + (tuple(dev),)
         if not self.state:
-            hflat = np.zeros(g.stride, dtype=np.float32)
-            tflat = np.zeros(g.stride, dtype=np.float64)
-            for k in dev:
-                s = plan.key_segment[k]
-                hflat[s.offset : s.offset + s.numel] = np.asarray(_as_host(self.h_host[k])).reshape(-1)
-                t0 = np.asarray(self._theta_init[k], dtype=np.float64).reshape(-1)
-                tflat[s.offset : s.offset + s.numel] = t0
-            self.state = {
-                sh.index: (torch.from_numpy(hflat[sh.c0 : sh.c1].copy()).to(sh.device),
-                           torch.from_numpy(tflat[sh.c0 : sh.c1].copy()).to(sh.device, tdt))
-                for sh in shards
-            }
+            segs = [plan.key_segment[k] for k in dev]
+            hs = _to_shards(_flatten(g.stride, np.float32, segs, {k: _as_host(self.h_host[k]) for k in dev}), shards)
+            th = _to_shards(_flatten(g.stride, np.float64, segs, self._theta_init), shards, tdt)
+            self.state = {sh.index: (hs[sh.index], DoubleBuffer(th[sh.index])) for sh in shards}
             self._sig, self._tdt = sig, tdt
         elif sig != self._sig:
             raise ValueError("model layout changed between FedDyn rounds; set h again")
@@ -604,25 +597,25 @@ class DynState:
             raise TypeError("FedDyn: the weights' type changed between rounds (theta precision)")
         self.dev_keys, self.skipped = tuple(dev), tuple(skip)
         self._covered = len(dev) == len(g.segments)
-        self._plan_f32 = g
+        self._plan = plan
         return True
 
     def step(self, agg: "Aggregator", sh, stack, w, nm: Numerics, want64: bool):
         """The fused round for one shard: returns the output tensor (theta itself for f64)."""
-        hs, th = self.state[sh.index]
+        hs, theta = self.state[sh.index]
+        th = theta.cur
         f64 = th.dtype == torch.float64
         self._dirty = True
         if self._covered:
             out32 = None if want64 else agg.packer.device_bucket(("out32", KIND_F32, sh.index), (sh.width,),
                                                                    torch.float32, sh.device)
-            # theta double-buffered (read one, write the other, swap; DESIGN.md §4 finding 20); h, the
-            # caller-visible state synced back by sync_h, stays in place
-            th_o = self._spare.get(sh.index)
-            if th_o is None or th_o.shape != th.shape or th_o.dtype != th.dtype or th_o.device != th.device:
-                th_o = torch.empty_like(th)
+            # theta double-buffered (read one, write the other, advance once the launch call has
+            # returned; DESIGN.md §4 finding 20); h, the caller-visible state synced back by sync_h,
+            # stays in place
+            th_o = theta.other
             reduce_stack(stack, w, nm.mode, nm.denom, out32=out32, out64=th_o if want64 else None,
                          op=na.OP_DYN, v=th, v_out=th_o, h=hs, alpha=self.alpha)
-            self.state[sh.index], self._spare[sh.index] = (hs, th_o), th
+            theta.flip()
             return th_o if want64 else out32
         # partial coverage: mean in theta's precision, then the update on the covered runs
         gbuf = agg.packer.device_bucket(("dyn_g", KIND_F32, sh.index), (sh.width,), th.dtype, sh.device)
@@ -637,7 +630,7 @@ class DynState:
 
     def _runs(self, sh):
         """Maximal column runs [a, b) of device keys within the shard, shard-relative."""
-        segs = sorted((s.offset, s.offset + s.numel) for s in self._plan_f32.segments if s.key in set(self.dev_keys))
+        segs = sorted((s.offset, s.offset + s.numel) for s in self._plan.f32.segments if s.key in set(self.dev_keys))
         runs = []
         for lo, hi in segs:
             lo, hi = max(lo, sh.c0), min(hi, sh.c1)
@@ -654,22 +647,15 @@ class DynState:
         """State i (0: h, 1: theta) over the whole bucket.  With a column-sharded process group
         every rank holds only its columns: this is then a collective (an all-gather) that every
         rank must call — reading `Dyn.h`, `set_h`, `set_theta` included."""
-        if self.group is not None:
-            from .bucket import rank_width
-            from .dist import gather_columns
-
-            (loc,) = [self.state[j][i] for j in sorted(self.state)]
-            group, world = self.group
-            stride = self._plan_f32.stride
-            return gather_columns(loc, rank_width(stride, world), stride, group).cpu().numpy()
-        return np.concatenate([self.state[j][i].cpu().numpy() for j in sorted(self.state)])
+        cols = [self.state[j][i] if i == 0 else self.state[j][i].cur for j in sorted(self.state)]
+        return _bucket_host(cols, self._plan.f32.stride, self.group)
 
     def sync_h(self):
         """Copy the device h into the caller's arrays (in place) and return the dict."""
         if self._dirty and self.state:
             flat = self._host_flat(0)
             for k in self.dev_keys:
-                s = self._plan_f32_segment(k)
+                s = self._plan.key_segment[k]
                 val = flat[s.offset : s.offset + s.numel].reshape(s.shape)
                 dst = self.h_host[k]
                 if isinstance(dst, torch.Tensor):
@@ -683,15 +669,9 @@ class DynState:
         flat = self._host_flat(1)
         out = dict(self._theta_init)
         for k in self.dev_keys:
-            s = self._plan_f32_segment(k)
+            s = self._plan.key_segment[k]
             out[k] = flat[s.offset : s.offset + s.numel].reshape(s.shape).copy()
         return out
-
-    def _plan_f32_segment(self, k):
-        for s in self._plan_f32.segments:
-            if s.key == k:
-                return s
-        raise KeyError(k)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -699,6 +679,34 @@ class DynState:
 # ---------------------------------------------------------------------------------------------
 
 OUTPUTS = ("reference", "float32", "device")
+
+
+class _SmallChain(NamedTuple):
+    """The fp32 bucket of a small zero-copy round as chained launches (Aggregator._small_chain)."""
+    pack: AsyncPack  # native threads pack part k's clients as its chunk k
+    launches: list  # the ctypes arguments of launch k
+    weights: list  # launch k's device weights, kept alive
+
+
+class _SmallBucket(NamedTuple):
+    """One bucket kind of a small round's record (Aggregator._small_record)."""
+    nat: NativeRows  # the native pack table of every client into `host`
+    host: torch.Tensor  # pinned staging, [clients (+ a chain's partial-sum rows), stride]
+    stack: torch.Tensor  # what the kernel reads: `host` itself (zero-copy) or a device stack
+    w: torch.Tensor  # device weights, kept alive
+    dout: torch.Tensor  # what the kernel writes: `hout` itself (zero-copy) or a device buffer
+    hout: torch.Tensor  # the pinned result ...
+    hnp: np.ndarray  # ... and its numpy view
+    fn: object  # the reduce entry point
+    args: tuple  # its ctypes arguments, all but the stream
+    out: list  # (key, offset, size, shape) of every key of the result
+    chain: _SmallChain | None
+
+
+class _SmallRecord(NamedTuple):
+    buckets: tuple  # one _SmallBucket per bucket kind
+    pack: object  # fa_py_pack_rows
+    wsig: tuple | None  # the fp32 bucket's layout as wire.wire_row compares it
 
 
 class Aggregator:
@@ -746,16 +754,14 @@ class Aggregator:
         # packs and reduces only its columns of the fp32 bucket and an RCCL all-gather over xGMI
         # reassembles the global model on every rank.  True = the default process group.
         self.group = None
-        if group is not None:
+        self._dist = group is not None
+        if self._dist:
             import torch.distributed as dist
 
             self.group = None if group is True else group
             if not dist.is_initialized():
                 raise RuntimeError("group= needs torch.distributed initialised (one process per GPU)")
             self.packer.rank_cols = (dist.get_rank(self.group), dist.get_world_size(self.group))
-            self._dist = True
-        else:
-            self._dist = False
         self.last_plan: BucketPlan | None = None
         self._wcache = {}  # (device, dtype, bytes) -> device weights: a pageable H2D per round saved
 
@@ -848,26 +854,24 @@ class Aggregator:
         rec = plan.memo.get(key)
         if rec is not None:
             return rec or None
-        from .bucket import _FMT, SMALL_BYTES, AsyncPack, Packer, Shard, _NativeRows, _STORE, _TORCH
-
         n = plan.n_clients
-        total = sum(n * g.stride * np.dtype(_STORE[k]).itemsize for k, g in plan.groups.items())
+        total = sum(n * g.stride * np.dtype(g.store_dtype).itemsize for g in plan.groups.values())
         # (a float16 bucket takes the general path: its result dtype depends on the output mode)
         if plan.input_kind != "numpy" or total >= SMALL_BYTES or not plan.groups or KIND_F16 in plan.groups:
             plan.memo[key] = False
             return None
         L, dev = na.lib(), self.device
-        kinds = []
+        buckets = []
         for kind, g in plan.groups.items():
-            tdt = _TORCH[_STORE[kind]]
+            tdt = TORCH_DTYPE[g.store_dtype]
             pieces = Packer._pieces(g, [Shard(0, dev, 0, g.stride)])
             # spare rows: the chained zero-copy round's partial sums (below)
             parts = max(1, min(int(self.small_parts), n // 2))
             host = torch.zeros((n + parts - 1, g.stride), dtype=tdt, pin_memory=True)
-            if not _NativeRows.usable(pieces, [host]):
+            if not NativeRows.usable(pieces, [host]):
                 plan.memo[key] = False
                 return None
-            nat = _NativeRows(pieces, [host], w_local_lst, [None] * n)
+            nat = NativeRows(pieces, [host], w_local_lst, [None] * n)
             nm = g.numerics
             w = self._weights(nm, dev)
             f64 = kind != KIND_F32 or (self.output == "reference" and nm.out_dtype == _F64)
@@ -878,25 +882,25 @@ class Aggregator:
             else:
                 stack = torch.empty((n, g.stride), dtype=tdt, device=dev)
                 dout = torch.empty(g.stride, dtype=odt, device=dev)
-            split = None
+            chain = None
             if kind == KIND_F32:
                 fn = L.fa_reduce_f32
                 args = (stack.data_ptr(), g.stride, n, nm.mode, w.data_ptr(), float(nm.denom), 0, g.stride, None,
                         None if f64 else dout.data_ptr(), dout.data_ptr() if f64 else None)
                 if zc and parts >= 2 and nm.mode in (na.MODE_W32_DIV64, na.MODE_W32_DIV32):
-                    split = self._small_chain(g, pieces, host, w, nm, dout, f64, n, parts, dev, AsyncPack, _FMT)
+                    chain = self._small_chain(g, pieces, host, w, nm, dout, f64, n, parts, dev)
             else:
                 fn = L.fa_reduce_f64 if kind == KIND_F64 else L.fa_reduce_i64
                 args = (stack.data_ptr(), g.stride, n, w.data_ptr(), float(nm.denom), 0, g.stride, dout.data_ptr())
             out = [(s.key, s.offset, s.numel, s.shape) for s in g.segments]
-            kinds.append((nat, host, stack, w, dout, hout, hout.numpy(), fn, args, out, split))
+            buckets.append(_SmallBucket(nat, host, stack, w, dout, hout, hout.numpy(), fn, args, out, chain))
         g32 = plan.groups.get(KIND_F32)
         wsig = (tuple((s.key, s.shape, s.offset) for s in g32.segments) + (g32.stride,)) if g32 is not None else None
-        rec = plan.memo[key] = (tuple(kinds), na.load_pyhost().fa_py_pack_rows, wsig)
+        rec = plan.memo[key] = _SmallRecord(tuple(buckets), na.load_pyhost().fa_py_pack_rows, wsig)
         return rec
 
     @staticmethod
-    def _small_chain(g, pieces, host, w, nm, dout, f64, n, parts, dev, AsyncPack, fmt_of):
+    def _small_chain(g, pieces, host, w, nm, dout, f64, n, parts, dev) -> _SmallChain:
         """The fp32 bucket of a small zero-copy round as `parts` chained launches.  Clients are cut
         into parts b_0 = 0 < b_1 < ... < b_K = n (the first smallest, so the GPU starts early);
         client i of part k sits in staging row i + k.  Launch 0 sums rows [0, b_1) in fp32 (mode
@@ -905,8 +909,7 @@ class Aggregator:
         k's clients — into row b_{k+1} + k, the last one with the real denominator and output.
         fl32(1 * acc) = acc, so the chain of adds is the single launch's, bit for bit, and no
         launch writes a row it reads.  The parts are packed by native threads
-        (AsyncPack chunk k = part k) and each launch waits only for its own part.
-        Returns ("chain", AsyncPack, [launch args], [weight tensors kept alive])."""
+        (AsyncPack chunk k = part k) and each launch waits only for its own part."""
         base, rem = divmod(n, parts)
         sizes = [base] * parts
         for j in range(rem):  # the remainder goes to the last parts
@@ -921,7 +924,7 @@ class Aggregator:
             for i in range(bounds[k], bounds[k + 1]):
                 for s, a, b, _sh, d in pieces:
                     it = s.src_dtype.itemsize
-                    rows.append((i, s.numel * it, fmt_of[s.src_dtype], hp + (i + k) * row + d * it, k, a * it,
+                    rows.append((i, s.numel * it, FMT[s.src_dtype], hp + (i + k) * row + d * it, k, a * it,
                                  (b - a) * it))
         keys = tuple(s.key for s, *_ in pieces) * n
         ap = AsyncPack(keys, np.array(rows, dtype=np.int64).reshape(-1, 7), parts)
@@ -941,7 +944,7 @@ class Aggregator:
             else:
                 args.append((first, g.stride, cnt, nm.mode, wk.data_ptr(), float(nm.denom), 0, g.stride, None,
                              None if f64 else dout.data_ptr(), dout.data_ptr() if f64 else None))
-        return ("chain", ap, args, ws)
+        return _SmallChain(ap, args, ws)
 
     def _small_round(self, plan: BucketPlan, w_local_lst):
         """One small host round with no per-key Python: the uploads are packed natively into the
@@ -954,68 +957,65 @@ class Aggregator:
         rec = self._small_record(plan, w_local_lst)
         if rec is None:
             return None
-        kinds, pack, wsig = rec
+        buckets = rec.buckets
         lst = w_local_lst if type(w_local_lst) is list else list(w_local_lst)
-        if wsig is not None:
-            from .wire import wire_row
-
-            if wire_row(lst[0], wsig) is not None:  # decoded by the wire codec into pinned rows of
-                return None                          # this layout: the general path DMAs them as is
+        # decoded by the wire codec into pinned rows of this layout: the general path DMAs them as is
+        if rec.wsig is not None and wire_row(lst[0], rec.wsig) is not None:
+            return None
         n = len(lst)
-        for nat, *rest in kinds:  # every bucket packed here, except a chained one (native threads)
-            if rest[-1] is None and pack(lst, nat.keys, len(nat.keys), nat.ptr, 0, n) != 0:
+        for b in buckets:  # every bucket packed here, except a chained one (native threads)
+            if b.chain is None and rec.pack(lst, b.nat.keys, len(b.nat.keys), b.nat.ptr, 0, n) != 0:
                 return None
         handles = {}
         try:
-            for i, (nat, *rest) in enumerate(kinds):
-                if rest[-1] is not None:
-                    h = rest[-1][1].start(lst)
+            for i, b in enumerate(buckets):
+                if b.chain is not None:
+                    h = b.chain.pack.start(lst)
                     if h is None:  # a value off the plan: nothing was copied, nothing launched
                         return None
                     handles[i] = h
             dev = self.device
             if dev.index is not None and dev.index != torch.cuda.current_device():
                 with torch.cuda.device(dev):  # launches go to dev's stream from dev's context
-                    parts = self._small_launch(kinds, handles, dev)
+                    parts = self._small_launch(buckets, handles, dev)
             else:
-                parts = self._small_launch(kinds, handles, dev)
+                parts = self._small_launch(buckets, handles, dev)
         finally:
             for i, h in handles.items():  # every copy done (and the values released)
-                kinds[i][-1][1].end(h)
+                buckets[i].chain.pack.end(h)
         return {k: parts[k] for k in plan.keys}
 
-    def _small_launch(self, kinds, handles, dev):
+    def _small_launch(self, buckets, handles, dev):
         """The queued part of _small_round: launches (and copies) on dev's current stream — a
         chained bucket's launches each right after its part's copies are in — one
         synchronisation, the results as {key: value}."""
         stream = torch.cuda.current_stream(dev)
         sh = stream.cuda_stream
         try:
-            self._small_enqueue(kinds, handles, stream, sh)
+            self._small_enqueue(buckets, handles, stream, sh)
         finally:
             stream.synchronize()  # also: the staging may be rewritten by the next call
         parts = {}
-        for nat, host, stack, w, dout, hout, hnp, fn, args, out, split in kinds:
-            fresh = hnp.copy()
-            for k, off, m, shape in out:
+        for b in buckets:
+            fresh = b.hnp.copy()
+            for k, off, m, shape in b.out:
                 a = fresh[off : off + m].reshape(shape)
                 parts[k] = a.dtype.type(a[()]) if shape == () else a
         return parts
 
-    def _small_enqueue(self, kinds, handles, stream, sh):
-        for i, (nat, host, stack, w, dout, hout, hnp, fn, args, out, split) in enumerate(kinds):
-            if split is not None:  # chained zero-copy launches, each after its part is packed
-                _, ap, chain, _ws = split
-                for k, a in enumerate(chain):
-                    ap.wait(handles[i], k)
+    def _small_enqueue(self, buckets, handles, stream, sh):
+        for i, b in enumerate(buckets):
+            fn = b.fn
+            if b.chain is not None:  # chained zero-copy launches, each after its part is packed
+                for k, a in enumerate(b.chain.launches):
+                    b.chain.pack.wait(handles[i], k)
                     na.check(fn(*a, sh), fn.__name__)
-                continue
-            if stack is host:  # zero-copy record
-                na.check(fn(*args, sh), fn.__name__)
-                continue
-            stack.copy_(host[: stack.shape[0]], non_blocking=True)
-            na.check(fn(*args, sh), fn.__name__)
-            hout.copy_(dout, non_blocking=True)
+            elif b.stack is b.host:  # zero-copy record
+                na.check(fn(*b.args, sh), fn.__name__)
+            else:
+                b.stack.copy_(b.host[: b.stack.shape[0]], non_blocking=True)
+                na.check(fn(*b.args, sh), fn.__name__)
+                b.hout.copy_(b.dout, non_blocking=True)
 
     def _gather_columns(self, plan: BucketPlan, parts):
         """Column-sharded group: every rank's reduced columns -> the whole f32 bucket on every
@@ -1026,9 +1026,6 @@ class Aggregator:
         gather moves P*4 bytes instead of P*8, and one 1-client reduce of the gathered sums
         (weight fl32(1.0), W = np.sum(weights)) then computes fl64(acc)/W — the value the
         unsharded kernel's epilogue computes, bit for bit."""
-        from .bucket import Shard, rank_width
-        from .dist import gather_columns
-
         (sh, out), = parts
         stride = plan.groups[KIND_F32].stride
         full = gather_columns(out[: sh.width], rank_width(stride, self.packer.rank_cols[1]), stride, self.group)
@@ -1061,15 +1058,13 @@ class Aggregator:
             return server_opt.step(self, sh, stack, w, nm, want64)
         if server_opt is not None and fused:
             # fused: fl32(w) becomes the next round's prev (the model clients load), v_t advances;
-            # both into the spare pair, which then becomes the state (double-buffered)
-            prev, v, prev_o, v_o = server_opt.swap_buffers(sh)
-            try:
-                reduce_stack(stack, w, nm.mode, nm.denom, out32=prev_o, out64=out64, op=server_opt.op, prev=prev,
-                             v=v, v_out=v_o, beta=server_opt.beta, eta=server_opt.eta, tau=server_opt.tau,
-                             beta2=server_opt.beta2, reorder=self.reorder and not isinstance(stack, RowTable))
-            except BaseException:
-                server_opt.unswap(sh)  # a refused launch must not leave the state on the empty spare pair
-                raise
+            # both into the other pair, which becomes the state only once the launch call has returned
+            # (double-buffered: a refused launch leaves the state on the pair it had)
+            prev, v, prev_o, v_o = server_opt.step_buffers(sh)
+            reduce_stack(stack, w, nm.mode, nm.denom, out32=prev_o, out64=out64, op=server_opt.op, prev=prev,
+                         v=v, v_out=v_o, beta=server_opt.beta, eta=server_opt.eta, tau=server_opt.tau,
+                         beta2=server_opt.beta2, reorder=self.reorder and not isinstance(stack, RowTable))
+            server_opt.advance(sh)
             return out64 if want64 else prev_o
         out32 = None
         if not want64 or server_opt is not None:

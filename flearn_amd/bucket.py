@@ -39,11 +39,11 @@ STRIDE_ALIGN_F16 = 128  # elements: the float16 row stride is a multiple of 256 
 SMALL_BYTES = 4 << 20  # below this, host packing / unpacking runs on the calling thread
 
 _STORE = {KIND_F32: np.float32, KIND_F64: np.float64, KIND_I64: np.int64, KIND_F16: np.float16}
-_TORCH = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64, np.float16: torch.float16}
+TORCH_DTYPE = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64, np.float16: torch.float16}
 # device-upload dtypes a group's row table takes, and their fa_gather_rows_f64 source kind
 _ROW_SOURCES = {torch.float64: {torch.float64: na.SRC_F64, torch.int64: na.SRC_I64, torch.float32: na.SRC_F32}}
 _NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int64: np.int64, torch.float16: np.float16}
-_FMT = {np.dtype(np.float32): ord("f"), np.dtype(np.float64): ord("d"), np.dtype(np.int64): ord("i"),
+FMT = {np.dtype(np.float32): ord("f"), np.dtype(np.float64): ord("d"), np.dtype(np.int64): ord("i"),
         np.dtype(np.float16): ord("e")}
 
 
@@ -91,7 +91,7 @@ class AsyncPack:
         self.L.fa_py_pack_end(h)
 
 
-class _NativeRows:
+class NativeRows:
     """Packs client rows through fa_py_pack_rows (csrc/fa_pyhost.c): one native call walks the
     clients' dicts and copies every piece into the pinned staging, the GIL released around the
     copies.  Built per pack call from the plan's pieces; `__call__(lo, hi)` returns False when a
@@ -112,7 +112,7 @@ class _NativeRows:
         if cached is None:
             # per piece: itemsize, numel, src lo, src hi, format, dst base, dst row stride
             # (elements), dst off -> the byte table fa_py_pack_rows reads (7 rows of pieces)
-            t = np.array([(s.src_dtype.itemsize, s.numel, a, b, _FMT[s.src_dtype]) + hp[sh.index] + (d,)
+            t = np.array([(s.src_dtype.itemsize, s.numel, a, b, FMT[s.src_dtype]) + hp[sh.index] + (d,)
                           for s, a, b, sh, d in pieces], dtype=np.int64).reshape(-1, 8).T
             item = t[0]
             table = np.concatenate([t[1] * item, t[2] * item, (t[3] - t[2]) * item, t[4], t[5],
@@ -129,11 +129,14 @@ class _NativeRows:
     def usable(pieces, hosts) -> bool:
         """Byte copies only: every source dtype is its bucket's storage dtype."""
         return bool(pieces) and all(
-            h is not None and s.src_dtype in _FMT and np.dtype(_NP[h.dtype]) == s.src_dtype
+            h is not None and s.src_dtype in FMT and np.dtype(_NP[h.dtype]) == s.src_dtype
             for s, _, _, sh, _ in pieces for h in (hosts[sh.index],))
 
     def __call__(self, lo: int, hi: int) -> bool:
         return self.fn(self.clients, self.keys, len(self.keys), self.ptr, lo, hi) == 0
+
+
+_NativeRows = NativeRows  # its name before the aggregator imported it at module level
 
 
 @dataclass
@@ -387,6 +390,7 @@ class Packer:
         self._dev = {}
         self._shards = {}
         self._pool = None
+        self._held = []  # (event, uploads read by launches queued before it): see hold()
         self.last_wire_rows = 0
         self.last_wire_staged = 0
         self.last_row_tables = {}  # kind -> "slab" | "rows" | "gather" | "copy" for device-resident uploads
@@ -427,7 +431,7 @@ class Packer:
     def hold(self, objs, device) -> None:
         """Keep `objs` (uploads read by queued launches) alive until the work queued so far on
         `device`'s current stream is done; earlier holds whose events completed are dropped."""
-        self._held = [(e, o) for e, o in getattr(self, "_held", []) if not e.query()]
+        self._held = [(e, o) for e, o in self._held if not e.query()]
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(device))
         self._held.append((ev, objs))
@@ -472,7 +476,7 @@ class Packer:
         self.last_row_tables = {}
         self.last_pack_paths = {}
         for kind, g in plan.groups.items():
-            tdt = _TORCH[g.store_dtype]
+            tdt = TORCH_DTYPE[g.store_dtype]
             shards = self.shards(plan, kind)
             devs = [self.device_bucket(("in", kind, sh.index), (plan.n_clients, sh.width), tdt, sh.device)
                     for sh in shards]
@@ -572,7 +576,7 @@ class Packer:
         if len(shards) != 1 or shards[0].c0 != 0 or shards[0].c1 != g.stride:
             return None
         dev = shards[0].device
-        store = _TORCH[g.store_dtype]
+        store = TORCH_DTYPE[g.store_dtype]
         accept = _ROW_SOURCES.get(store, {store: na.SRC_F64})
         segs = [s for s in g.segments if s.numel > 0]
         w0 = w_local_lst[0]
@@ -624,8 +628,8 @@ class Packer:
         into a pinned row of this layout (`rows[n]`) skip the pack and are DMA'd from there."""
         rows = rows if rows is not None else [None] * plan.n_clients
         host_np = [h.numpy() if h is not None else None for h in hosts]
-        native = (_NativeRows(pieces, hosts, w_local_lst, rows, plan.memo)
-                  if _NativeRows.usable(pieces, hosts) else None)
+        native = (NativeRows(pieces, hosts, w_local_lst, rows, plan.memo)
+                  if NativeRows.usable(pieces, hosts) else None)
 
         def fill(n):
             if rows[n] is not None:
@@ -679,7 +683,7 @@ class Packer:
                     started.append((j, aps[j].start(lst)))
                 for j, (lo, hi) in enumerate(bounds):
                     _, h = started[0]
-                    if h is None:  # a value off the plan in this chunk: the _NativeRows / Python pack
+                    if h is None:  # a value off the plan in this chunk: the NativeRows / Python pack
                         fill_rows(lo, hi)
                         path = "mixed"
                     else:
@@ -723,7 +727,7 @@ class Packer:
         # per piece: value bytes, format, row-0 destination, row stride, first byte, bytes
         item = np.array([s.src_dtype.itemsize for s, *_ in pieces], dtype=np.int64)
         total = np.array([s.numel for s, *_ in pieces], dtype=np.int64) * item
-        fmt = np.array([_FMT[s.src_dtype] for s, *_ in pieces], dtype=np.int64)
+        fmt = np.array([FMT[s.src_dtype] for s, *_ in pieces], dtype=np.int64)
         dst0 = np.array([hp[sh.index][0] for _s, _a, _b, sh, _d in pieces], dtype=np.int64) + \
             np.array([d for *_x, d in pieces], dtype=np.int64) * item
         rstride = np.array([hp[sh.index][1] for _s, _a, _b, sh, _d in pieces], dtype=np.int64)

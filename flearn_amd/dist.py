@@ -932,29 +932,61 @@ class ShardPlan:
         return max(0, min(self.widths[stripe], self.n_cols - g0))
 
 
+class DoubleBuffer:
+    """A state tensor and its twin: a step reads `cur`, writes `other`, and `flip()` — called once
+    the launch returned, so a refused step changes nothing — makes what it wrote current (stores
+    onto just-loaded lines cost 1-3% per launch, DESIGN.md §4 finding 20).  The twin is allocated
+    when `other` is first asked for; buf[i] is buffer i of the pair, `index` the current one's."""
+
+    __slots__ = ("cur", "_other", "index")
+
+    def __init__(self, t: torch.Tensor):
+        self.cur, self._other, self.index = t, None, 0
+
+    @property
+    def other(self) -> torch.Tensor:
+        if self._other is None:
+            self._other = torch.empty_like(self.cur)
+        return self._other
+
+    def flip(self):
+        self.cur, self._other = self.other, self.cur
+        self.index ^= 1
+
+    def __getitem__(self, i: int) -> torch.Tensor:
+        return self.cur if i == self.index else self.other
+
+
 class PingPong:
     """Double-buffered state of a fused server step on one rank's columns (FedAVGM / FedOPT):
-    step k reads (prev[k % 2], v[k % 2]) and writes the global model and v_t into the other pair,
-    so the kernel's epilogue stores never land on the lines it has just loaded (in place costs
-    1-3% per launch, DESIGN.md §4 finding 20).  `out` is where the current step writes the fp32
-    model (the next step's prev); `flip()` advances after every stripe of a step is launched."""
+    step k reads (prev[k % 2], v[k % 2]) and writes the global model and v_t into the other pair
+    (two DoubleBuffers).  `out` is where the current step writes the fp32 model (the next step's
+    prev); `flip()` advances after every stripe of a step is launched."""
 
     def __init__(self, prev: torch.Tensor, v: torch.Tensor):
-        self.prev = [prev, torch.empty_like(prev)]
-        self.v = [v, torch.empty_like(v)]
-        self.cur = 0
+        self.prev, self.v = DoubleBuffer(prev), DoubleBuffer(v)
+
+    @property
+    def cur(self) -> int:
+        return self.v.index
+
+    @cur.setter
+    def cur(self, i: int):
+        for buf in (self.prev, self.v):
+            if buf.index != i:
+                buf.flip()
 
     @property
     def out(self) -> torch.Tensor:
-        return self.prev[1 - self.cur]
+        return self.prev.other
 
     def window(self, c0: int, n: int):
         """(prev, v, v_out) of local columns [c0, c0 + n) for the current step."""
-        i, o = self.cur, 1 - self.cur
-        return self.prev[i][c0 : c0 + n], self.v[i][c0 : c0 + n], self.v[o][c0 : c0 + n]
+        return self.prev.cur[c0 : c0 + n], self.v.cur[c0 : c0 + n], self.v.other[c0 : c0 + n]
 
     def flip(self):
-        self.cur ^= 1
+        self.prev.flip()
+        self.v.flip()
 
 
 class ShardedReducer:

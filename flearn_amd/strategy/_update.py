@@ -12,12 +12,16 @@ import ctypes
 import math
 import os
 import time
+from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from .. import _native as na
+from .. import aggregator  # its _epilogue / apply_update are called through the module (tests patch them there)
 from ..bucket import ALIGN, AsyncPack
+from ..dist import DoubleBuffer
 
 _FMT = {np.dtype(np.float32): ord("f"), np.dtype(np.float64): ord("d")}
 _F32 = np.dtype(np.float32)
@@ -87,6 +91,59 @@ class _DictPack:
         return all(rc == 0 for rc in _run(self.tasks(d)))
 
 
+class _Slot(NamedTuple):
+    """One key's place in the flat layout."""
+    key: str
+    shape: tuple
+    offset: int
+    numel: int
+
+
+class _Chunk(NamedTuple):
+    """A run of whole keys of the layout: one launch of the zero-copy paths."""
+    first: int  # its element range [first, end) of the flat layout
+    end: int
+    pack_l: _DictPack  # its own pack tables into the shared staging (the Python-pool pack)
+    pack_g: _DictPack
+    keys: list  # its _Slots
+
+
+@dataclass
+class _Staging:
+    """Pinned staging of one layout, and what is built on it: all dropped with it."""
+    lh: torch.Tensor  # w_local, float32
+    gh: torch.Tensor  # w_glob
+    oh: torch.Tensor | None  # the copy-engine path's result (made when that path first runs)
+    pack_l: _DictPack  # whole-layout pack tables
+    pack_g: _DictPack
+    chunks: list | None = None  # the zero-copy chunk plan
+    apacks: dict = field(default_factory=dict)  # with w_local? -> the chunk plan's native pack
+    dma: "_DmaBuffers | None" = None
+    devmodel: "_DevModel | None" = None
+
+
+class _DmaBuffers(NamedTuple):
+    """transfer = "dma": device copies of the staging and the result, the copy-in / copy-out streams."""
+    dl: torch.Tensor
+    dg: torch.Tensor
+    dout: torch.Tensor
+    s_in: torch.cuda.Stream
+    s_out: torch.cuda.Stream
+
+
+@dataclass
+class _DevModel:
+    """update_on_device's buffers: the gathered local model, w_glob and the result on the device,
+    the gather's segment table and its pointer table (pinned and device)."""
+    dev: torch.device
+    dl: torch.Tensor
+    dg: torch.Tensor
+    dout: torch.Tensor
+    segs: torch.Tensor
+    ptr_h: torch.Tensor
+    ptr_d: torch.Tensor
+
+
 class _AsyncPack(AsyncPack):
     """The zero-copy chunk plan's copies into the pinned staging as one native job list: per
     key, w_local's float32 value (when `lh_ptr` is given) and w_glob's value, in chunk order."""
@@ -95,8 +152,8 @@ class _AsyncPack(AsyncPack):
         item = torch.empty((), dtype=gdtype).element_size()
         gfmt = ord("d") if item == 8 else ord("f")
         keys, rows = [], []
-        for j, (_f, _e, _pl, _pg, g) in enumerate(chunks):
-            for k, _s, o, n in g:
+        for j, (*_, slots) in enumerate(chunks):  # _Chunks, or any tuples that end in their slots
+            for k, _s, o, n in slots:
                 if lh_ptr is not None:
                     keys.append(k)
                     rows.append((0, n * 4, ord("f"), lh_ptr + o * 4, j, 0, n * 4))
@@ -106,6 +163,48 @@ class _AsyncPack(AsyncPack):
 
     def start(self, local, glob):
         return super().start((local if local is not None else {}, glob))
+
+
+class _ChunkFeed:
+    """One call's packing of the chunk plan into the pinned staging.  Every chunk's copies are
+    queued at once, in chunk order: native threads (or, for values the native pack refuses, the
+    Python pool) stay busy whatever the chunk sizes, and each chunk's kernel is launched as soon
+    as its own copies are in.  local None: w_glob only."""
+
+    def __init__(self, ap: _AsyncPack | None, st: _Staging, local, glob):
+        self.ap, self.st, self.local, self.glob = ap, st, local, glob
+        self.h = ap.start(local, glob) if ap is not None else None
+        self.futs = None
+        if self.h is None:
+            pool = _pool()
+            self.futs = [([pool.submit(t) for t in c.pack_l.tasks(local)] if local is not None else [],
+                          [pool.submit(t) for t in c.pack_g.tasks(glob)]) for c in st.chunks]
+
+    def wait(self, j: int):
+        """Chunk j is in the staging."""
+        if self.h is not None:
+            return self.ap.wait(self.h, j)
+        for futs, host, src in zip(self.futs[j], (self.st.lh, self.st.gh), (self.local, self.glob)):
+            if any(f.result() for f in futs):  # a value the native pack refuses: copy in Python
+                for k, _s, o, n in self.st.chunks[j].keys:
+                    host.numpy()[o : o + n] = src[k].reshape(-1)
+
+    def end(self):
+        """Every copy is done: releases the values."""
+        if self.h is not None:
+            self.ap.end(self.h)
+
+    def abort(self, *streams):
+        """After an error: no pack may still write the staging, nor a queued chunk read it or
+        write its result."""
+        self.end()
+        if self.futs is not None:
+            futs = [f for fl, fg in self.futs for f in fl + fg]
+            for f in futs:
+                f.cancel()
+            concurrent.futures.wait(futs)
+        for s in streams:
+            s.synchronize()
 
 
 class DeviceUpdater:
@@ -136,22 +235,23 @@ class DeviceUpdater:
         self.device = device
         self.params = dict(beta=beta, eta=eta, tau=tau, beta2=beta2)
         self.layout = None  # [(key, shape, offset, numel)]
-        self.v = None
-        self._v_next = None  # the zero-copy path's second v_t buffer (double-buffered: all or nothing)
+        self.v = None  # v_t, a DoubleBuffer (the zero-copy paths: all or nothing; else in place)
         self.v_host = {}  # v_t of the keys computed on the host (integer buffers, scalars)
-        self._stage = None  # pinned staging of the current layout (local, global, result)
+        self._stage = None  # the _Staging of the current layout
+        self._lay_cache = None  # (signature, layout, total) of the last w_glob
+        self._h2d_done = None  # update_on_device's last DMA out of the pinned staging
+        self.last_pack = None  # "native" | "pool": how the last host-model zero-copy call packed
 
     def _layout(self, w_glob):
         """[(key, shape, offset, numel)], total — cached on the (key, shape) signature: the same
         model comes back every round."""
         sig = tuple((k, g.shape) for k, g in w_glob.items())
-        hit = getattr(self, "_lay_cache", None)
-        if hit is not None and hit[0] == sig:
-            return hit[1], hit[2]
+        if self._lay_cache is not None and self._lay_cache[0] == sig:
+            return self._lay_cache[1:]
         lay, off = [], 0
         for k, shape in sig:
             n = math.prod(shape) if shape else 1
-            lay.append((k, shape, off, n))
+            lay.append(_Slot(k, shape, off, n))
             off += -(-max(n, 1) // ALIGN) * ALIGN
         self._lay_cache = (sig, lay, off)
         return lay, off
@@ -159,13 +259,13 @@ class DeviceUpdater:
     def reset(self):
         """Forget v_t (device and host keys): the next call starts from zeros, as a fresh
         strategy object would."""
-        self.layout, self.v, self._v_next, self._stage, self.v_host = None, None, None, None, {}
+        self.layout, self.v, self._stage, self.v_host = None, None, None, {}
 
     def state(self):
         """v_t as the reference exposes it: {key: ndarray}."""
         out = {}
         if self.v is not None:
-            host = self.v.cpu().numpy()
+            host = self.v.cur.cpu().numpy()
             out = {k: host[o : o + n].reshape(s).copy() for k, s, o, n in self.layout}
         out.update(self.v_host)
         return out
@@ -233,87 +333,80 @@ class DeviceUpdater:
             g = np.array([w_glob[k] for k in batch], dtype=np.float64)
             delta = g - lv
             v = np.array([vh[k] if k in vh else 0.0 for k in batch], dtype=np.float64)
-            if self.op == na.OP_AVGM:
-                v = delta + p["beta"] * v
-                out = lv + v
-            else:
-                sq = np.multiply(delta, delta)
-                if self.op == na.OP_ADAGRAD:
-                    v = v + sq
-                elif self.op == na.OP_YOGI:
-                    v = v - (1 - p["beta2"]) * sq * np.sign(v - sq)
-                else:
-                    v = p["beta2"] * v + (1 - p["beta2"]) * sq
-                out = lv + p["eta"] * delta / (np.sqrt(v) + p["tau"])
+            out, v = self._numpy_update(p, lv, delta, v)
             for i, k in enumerate(batch):
                 w_local[k] = out[i]
                 vh[k] = v[i]
             done = set(batch)
             keys = [k for k in keys if k not in done]
         for k in keys:
-            lv = w_local[k]
-            if isinstance(lv, torch.Tensor):
-                lv = lv.detach().cpu().numpy()
-            g = w_glob[k]
-            if isinstance(g, torch.Tensor):
-                g = g.detach().cpu().numpy()
+            lv, g = aggregator._as_host(w_local[k]), aggregator._as_host(w_glob[k])
             delta = g - lv
             v = vh.get(k)
             if v is None:
                 v = np.zeros_like(delta)
-            if self.op == na.OP_AVGM:
-                v = delta + p["beta"] * v
-                w_local[k] = lv + v
-            else:
-                sq = np.multiply(delta, delta)
-                if self.op == na.OP_ADAGRAD:
-                    v = v + sq
-                elif self.op == na.OP_YOGI:
-                    v = v - (1 - p["beta2"]) * sq * np.sign(v - sq)
-                else:
-                    v = p["beta2"] * v + (1 - p["beta2"]) * sq
-                w_local[k] = lv + p["eta"] * delta / (np.sqrt(v) + p["tau"])
-            vh[k] = v
+            w_local[k], vh[k] = self._numpy_update(p, lv, delta, v)
 
-    def _device_step(self, w_local, glob, local, gdt, **override):
+    def _numpy_update(self, p, lv, delta, v):
+        """(new w_local, new v_t) by the reference's numpy expressions (avgm.py:28-35, opt.py:45-63)."""
+        if self.op == na.OP_AVGM:
+            v = delta + p["beta"] * v
+            return lv + v, v
+        sq = np.multiply(delta, delta)
+        if self.op == na.OP_ADAGRAD:
+            v = v + sq
+        elif self.op == na.OP_YOGI:
+            v = v - (1 - p["beta2"]) * sq * np.sign(v - sq)
+        else:
+            v = p["beta2"] * v + (1 - p["beta2"]) * sq
+        return lv + p["eta"] * delta / (np.sqrt(v) + p["tau"]), v
+
+    def _bind(self, glob, tdt, dev) -> tuple:
+        """(layout, total, staging) of this call: v_t (zeros on first use, np.zeros_like(delta)) and
+        the pinned staging bound to w_glob's layout and dtype; a change of either raises."""
         lay, total = self._layout(glob)
-        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
-        tdt = torch.float64 if gdt == np.float64 else torch.float32
-        if self.v is not None and (self.layout != lay or self.v.dtype != tdt):
+        if self.v is not None and (self.layout != lay or self.v.cur.dtype != tdt):
             raise ValueError("the model layout or w_glob's dtype changed between rounds: v_t no longer matches; "
                              "call reset() to start the optimizer state afresh")
         if self.v is None:
             self.layout = lay
-            self.v = torch.zeros(total, dtype=tdt, device=dev)  # np.zeros_like(delta) on first use
-            self._v_next = None
+            self.v = DoubleBuffer(torch.zeros(total, dtype=tdt, device=dev))
             self._stage = None
-        st = self._staging(lay, total, tdt, dev)
-        ev = getattr(self, "_h2d_done", None)
-        if ev is not None:  # update_on_device's DMAs out of the shared pinned staging are done
-            ev.synchronize()
+        if self._stage is None:  # made once per layout, and zeroed once: only the segments are ever
+            # written, so the alignment gaps stay zero
+            lh = torch.zeros(total, dtype=torch.float32, pin_memory=True)
+            gh = torch.zeros(total, dtype=tdt, pin_memory=True)
+            gdt = np.float64 if tdt == torch.float64 else np.float32
+            self._stage = _Staging(lh, gh, None, _DictPack(lay, np.float32, lh.data_ptr()),
+                                   _DictPack(lay, gdt, gh.data_ptr()))
+        if self._h2d_done is not None:  # update_on_device's DMAs out of the shared pinned staging are done
+            self._h2d_done.synchronize()
             self._h2d_done = None
+        return lay, total, self._stage
+
+    def _device_step(self, w_local, glob, local, gdt, **override):
+        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        tdt = torch.float64 if gdt == np.float64 else torch.float32
+        lay, total, st = self._bind(glob, tdt, dev)
         if self.zero_copy:
             return self._device_step_zc(w_local, glob, local, lay, total, tdt, dev, **override)
-        lh, gh, oh, pack_l, pack_g = st
-        if oh is None:  # staging made for the zero-copy path: the copy-engine path needs a result buffer
-            oh = torch.empty(total, dtype=tdt, pin_memory=True)
-            self._stage = (lh, gh, oh, pack_l, pack_g)
+        if st.oh is None:
+            st.oh = torch.empty(total, dtype=tdt, pin_memory=True)
+        lh, gh, oh = st.lh, st.gh, st.oh
         with torch.cuda.device(dev):
             # local -> pinned -> device, then the global model while the local one is in flight
-            if not pack_l(local):
+            if not st.pack_l(local):
                 for k, s, o, n in lay:
                     lh.numpy()[o : o + n] = local[k].reshape(-1)
             ld = lh.to(dev, non_blocking=True)
-            if not pack_g(glob):
+            if not st.pack_g(glob):
                 for k, s, o, n in lay:
                     gh.numpy()[o : o + n] = glob[k].reshape(-1)
             gd = gh.to(dev, non_blocking=True)
             out = torch.empty(total, dtype=tdt, device=dev)
-            from ..aggregator import apply_update
-
             params = dict(self.params, **override)
             kw = {"out64": out} if tdt == torch.float64 else {"out32": out}
-            apply_update(self.op, ld, gd, self.v, **kw, **params)
+            aggregator.apply_update(self.op, ld, gd, self.v.cur, **kw, **params)
             oh.copy_(out, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()  # staging is reused by the next call
         # one fresh array for the new w_local, filled from the pinned result by the pool
@@ -325,17 +418,17 @@ class DeviceUpdater:
             w_local[k] = fresh[o : o + n].reshape(s)
 
     def _chunks(self, lay, total, tdt):
-        """[(first, end, pack_local, pack_glob)]: runs of whole keys of about chunk_bytes of w_glob,
-        in layout order, with their own pack tables into the shared staging (cached per layout)."""
-        if getattr(self, "_chunk_plan", None) is not None and self._chunk_plan[0] is self._stage:
-            return self._chunk_plan[1]
-        lh, gh = self._stage[0], self._stage[1]
+        """The staging's chunk plan, [_Chunk]: runs of whole keys of about chunk_bytes of w_glob, in
+        layout order, with their own pack tables into the shared staging (made once per staging)."""
+        st = self._stage
+        if st.chunks is not None:
+            return st.chunks
         gdt = np.float64 if tdt == torch.float64 else np.float32
         item = np.dtype(gdt).itemsize
         # target sizes: first_chunk_bytes doubling up to chunk_bytes, then chunk_bytes, and the
         # last ones halving down to last_chunk_bytes (the exposed ends of the pipeline: the first
         # chunk's pack before the GPU starts, the last chunk's kernel after the pack is done)
-        total_b = sum(e[3] for e in lay) * item
+        total_b = sum(n for _k, _s, _o, n in lay) * item
         head, b = [], max(1, int(self.first_chunk_bytes))
         while b < self.chunk_bytes and sum(head) + b < total_b:
             head.append(b)
@@ -350,131 +443,95 @@ class DeviceUpdater:
         groups, cur, size = [], [], 0
         for e in lay:
             cur.append(e)
-            size += e[3] * item
+            size += e.numel * item
             if size >= targets[min(len(groups), len(targets) - 1)]:
                 groups.append(cur)
                 cur, size = [], 0
         if cur:
             groups.append(cur)
-        out = []
-        for j, g in enumerate(groups):
-            first = g[0][2] if j else 0
-            end = groups[j + 1][0][2] if j + 1 < len(groups) else total
-            out.append((first, end, _DictPack(g, np.float32, lh.data_ptr(), 4 << 20),
-                        _DictPack(g, gdt, gh.data_ptr(), 4 << 20), g))
-        self._chunk_plan = (self._stage, out)
-        self._apacks = {}
-        return out
+        bounds = [0] + [g[0].offset for g in groups[1:]] + [total]
+        st.chunks = [_Chunk(bounds[j], bounds[j + 1], _DictPack(g, np.float32, st.lh.data_ptr(), 4 << 20),
+                            _DictPack(g, gdt, st.gh.data_ptr(), 4 << 20), g) for j, g in enumerate(groups)]
+        return st.chunks
 
-    def _apack(self, chunks, with_local: bool):
-        """The chunk plan's native async pack (w_glob only, or w_local and w_glob), cached with it."""
-        ap = self._apacks.get(with_local)
-        if ap is None:
-            ap = self._apacks[with_local] = _AsyncPack(chunks, self._stage[0].data_ptr() if with_local else None,
-                                                       self._stage[1].data_ptr(), self._stage[1].dtype)
-        return ap
+    def _feed(self, local, glob) -> _ChunkFeed:
+        """Start packing the chunk plan (w_glob only, or w_local and w_glob): the native async pack,
+        made once per staging, or the Python pool."""
+        st = self._stage
+        ap = None
+        if self.native_pack:
+            ap = st.apacks.get(local is not None)
+            if ap is None:
+                ap = st.apacks[local is not None] = _AsyncPack(
+                    st.chunks, st.lh.data_ptr() if local is not None else None, st.gh.data_ptr(), st.gh.dtype)
+        return _ChunkFeed(ap, st, local, glob)
 
     def _device_step_zc(self, w_local, glob, local, lay, total, tdt, dev, **override):
         """All or nothing: v_t advances into the second buffer, which becomes v_t only after
         every chunk ran; on any error the queued chunks are waited for (they read the staging
         the next call repacks) and v_t, the staging and w_local are as before the call."""
-        from ..aggregator import _epilogue
-
-        lh, gh = self._stage[0], self._stage[1]
+        st = self._stage
+        lh, gh = st.lh, st.gh
         L = na.lib()
         prec = na.PREC_F64 if tdt == torch.float64 else na.PREC_F32
         p = dict(self.params, **override)
-        if self._v_next is None or self._v_next.shape != self.v.shape or self._v_next.dtype != self.v.dtype:
-            self._v_next = torch.empty_like(self.v)
-        v_in, v_out = self.v, self._v_next
+        v_in, v_out = self.v.cur, self.v.other
         # the new w_local lives in a fresh pinned buffer the kernel writes over PCIe; the values
         # handed out are views of it (torch's host caching allocator recycles it once they die)
         t_alloc = time.perf_counter()
         res = torch.empty(total, dtype=tdt, pin_memory=True)
         dma = self.transfer in ("dma", "dma_in")
         dma_out = self.transfer == "dma"
-        if dma:
-            dbuf = getattr(self, "_dbuf", None)
-            if dbuf is None or dbuf[0] is not self._stage:
-                # device copies of the staging and the result, and the copy-in / copy-out streams
-                dbuf = self._dbuf = (self._stage, torch.empty(total, dtype=torch.float32, device=dev),
-                                     torch.empty(total, dtype=tdt, device=dev), torch.empty(total, dtype=tdt, device=dev),
-                                     torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-            _, dl, dg, dout, s_in, s_out = dbuf
+        if dma and st.dma is None:
+            st.dma = _DmaBuffers(torch.empty(total, dtype=torch.float32, device=dev),
+                                 torch.empty(total, dtype=tdt, device=dev), torch.empty(total, dtype=tdt, device=dev),
+                                 torch.cuda.Stream(dev), torch.cuda.Stream(dev))
+        d = st.dma
         tr = [] if self.trace is not None else None
         t0 = time.perf_counter()
         chunks = self._chunks(lay, total, tdt)
-        # every chunk's copies are queued at once, in chunk order: native threads (or, for values
-        # the native pack refuses, the Python pool) stay busy whatever the chunk sizes, and each
-        # chunk's kernel is launched as soon as its own copies are in
-        ap = self._apack(chunks, True) if self.native_pack else None
-        h = ap.start(local, glob) if ap is not None else None
-        self.last_pack = "native" if h is not None else "pool"
-        futs = None
-        if h is None:
-            pool = _pool()
-            futs = [([pool.submit(t) for t in pack_l.tasks(local)], [pool.submit(t) for t in pack_g.tasks(glob)])
-                    for _first, _end, pack_l, pack_g, _g in chunks]
+        feed = self._feed(local, glob)
+        self.last_pack = "native" if feed.h is not None else "pool"
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             sh = stream.cuda_stream
             try:
-                for j, (first, end, pack_l, pack_g, g) in enumerate(chunks):
+                for j, c in enumerate(chunks):
                     tp = time.perf_counter()
-                    if h is not None:
-                        ap.wait(h, j)
-                    else:
-                        fl, fg = futs[j]
-                        if any(f.result() for f in fl):  # a value the native pack refuses: copy in Python
-                            for k, s, o, n in g:
-                                lh.numpy()[o : o + n] = local[k].reshape(-1)
-                        if any(f.result() for f in fg):
-                            for k, s, o, n in g:
-                                gh.numpy()[o : o + n] = glob[k].reshape(-1)
-                    n = end - first
+                    feed.wait(j)
+                    first, end = c.first, c.end
                     if dma:  # copy engine in (own stream), the update on the device, copy engine out
-                        with torch.cuda.stream(s_in):
-                            dl[first:end].copy_(lh[first:end], non_blocking=True)
-                            dg[first:end].copy_(gh[first:end], non_blocking=True)
-                        stream.wait_stream(s_in)
-                        src_l, src_g = dl[first:end], dg[first:end]
-                        out = (dout if dma_out else res)[first:end].data_ptr()
+                        with torch.cuda.stream(d.s_in):
+                            d.dl[first:end].copy_(lh[first:end], non_blocking=True)
+                            d.dg[first:end].copy_(gh[first:end], non_blocking=True)
+                        stream.wait_stream(d.s_in)
+                        src_l, src_g = d.dl[first:end], d.dg[first:end]
+                        out = (d.dout if dma_out else res)[first:end].data_ptr()
                     else:  # the kernel reads the pinned staging and writes the pinned result over PCIe
                         src_l, src_g, out = lh[first:end], gh[first:end], res[first:end].data_ptr()
-                    epi = _epilogue(self.op, src_l, v_in[first:end], p["beta"], p["eta"], p["tau"], p["beta2"],
-                                    v_out=v_out[first:end])
+                    epi = aggregator._epilogue(self.op, src_l, v_in[first:end], p["beta"], p["eta"], p["tau"],
+                                               p["beta2"], v_out=v_out[first:end])
                     na.check(L.fa_opt_apply(prec, ctypes.byref(epi), src_l.data_ptr(), src_g.data_ptr(),
-                                            n, None if prec == na.PREC_F64 else out,
+                                            end - first, None if prec == na.PREC_F64 else out,
                                             out if prec == na.PREC_F64 else None, sh), "fa_opt_apply")
                     if dma_out:
-                        s_out.wait_stream(stream)
-                        with torch.cuda.stream(s_out):
-                            res[first:end].copy_(dout[first:end], non_blocking=True)
+                        d.s_out.wait_stream(stream)
+                        with torch.cuda.stream(d.s_out):
+                            res[first:end].copy_(d.dout[first:end], non_blocking=True)
                     if tr is not None:
                         tr.append((end - first, tp - t0, time.perf_counter() - t0))
             except BaseException:
-                if h is not None:  # no pack may still write the staging ...
-                    ap.end(h)
-                else:
-                    for fl, fg in futs:
-                        for f in fl + fg:
-                            f.cancel()
-                    concurrent.futures.wait([f for fl, fg in futs for f in fl + fg])
-                stream.synchronize()  # ... nor a queued chunk read it or write `res`
-                if dma:
-                    s_in.synchronize()
-                    s_out.synchronize()
+                feed.abort(stream, *((d.s_in, d.s_out) if dma else ()))
                 raise
             ts = time.perf_counter()
-            if h is not None:
-                ap.end(h)  # every copy is done: releases the values
+            feed.end()
             # the new values' views are made while the GPU finishes (they read nothing yet)
             fresh = res.numpy()
             views = [(k, fresh[o : o + n].reshape(s)) for k, s, o, n in lay]
             stream.synchronize()
             if dma:
-                s_out.synchronize()
-        self.v, self._v_next = v_out, v_in
+                d.s_out.synchronize()
+        self.v.flip()
         if tr is not None:
             self.trace.append({"chunks": tr, "launched_s": ts - t0, "done_s": time.perf_counter() - t0,
                                "alloc_s": t0 - t_alloc})
@@ -519,99 +576,53 @@ class DeviceUpdater:
         as it casts the reference's float64 host arrays.  Only the server's model crosses PCIe
         (the reference moves the local model down and the result back up as well).  v_t is the
         same double-buffered state the host path keeps, so the two paths may alternate."""
-        na.lib()
+        L = na.lib()
         glob = {k: np.ascontiguousarray(g) for k, g in w_glob.items()}
         gdt = next(iter(glob.values())).dtype
         tdt = torch.float64 if gdt == np.float64 else torch.float32
         dev = next(iter(local.values())).device
-        lay, total = self._layout(glob)
-        if self.v is not None and (self.layout != lay or self.v.dtype != tdt):
-            raise ValueError("the model layout or w_glob's dtype changed between rounds: v_t no longer matches; "
-                             "call reset() to start the optimizer state afresh")
-        if self.v is None:
-            self.layout = lay
-            self.v = torch.zeros(total, dtype=tdt, device=dev)
-            self._v_next = None
-            self._stage = None
-        self._staging(lay, total, tdt, dev)
-        gh = self._stage[1]
-        ev = getattr(self, "_h2d_done", None)
-        if ev is not None:  # the previous call's DMAs out of the pinned staging are complete
-            ev.synchronize()
-        key = ("devmodel", self._stage[1].data_ptr(), str(dev))
-        db = getattr(self, "_devbuf", None)
-        if db is None or db[0] != key:
+        lay, total, st = self._bind(glob, tdt, dev)
+        gh = st.gh
+        if st.devmodel is None or st.devmodel.dev != dev:
             segs = torch.tensor([o for _, _, o, _ in lay] + [n for _, _, _, n in lay], dtype=torch.int64).to(dev)
-            db = self._devbuf = (key, torch.zeros(total, dtype=torch.float32, device=dev),
-                                 torch.empty(total, dtype=tdt, device=dev), torch.empty(total, dtype=tdt, device=dev),
-                                 segs, torch.empty(len(lay), dtype=torch.int64, pin_memory=True),
-                                 torch.empty(len(lay), dtype=torch.int64, device=dev))
-        _, dl, dg, dout, segs, ptr_h, ptr_d = db
-        if self._v_next is None or self._v_next.shape != self.v.shape or self._v_next.dtype != self.v.dtype:
-            self._v_next = torch.empty_like(self.v)
-        v_in, v_out = self.v, self._v_next
-        from ..aggregator import _epilogue
-
-        L = na.lib()
+            st.devmodel = _DevModel(dev, torch.zeros(total, dtype=torch.float32, device=dev),
+                                    torch.empty(total, dtype=tdt, device=dev), torch.empty(total, dtype=tdt, device=dev),
+                                    segs, torch.empty(len(lay), dtype=torch.int64, pin_memory=True),
+                                    torch.empty(len(lay), dtype=torch.int64, device=dev))
+        db = st.devmodel
+        dl, dg, dout = db.dl, db.dg, db.dout
+        v_in, v_out = self.v.cur, self.v.other
         prec = na.PREC_F64 if tdt == torch.float64 else na.PREC_F32
         p = dict(self.params, **override)
         chunks = self._chunks(lay, total, tdt)
-        ap = self._apack(chunks, False) if self.native_pack else None
-        h = ap.start(None, glob) if ap is not None else None
-        futs = None
-        if h is None:
-            pool = _pool()
-            futs = [[pool.submit(t) for t in pack_g.tasks(glob)] for _f, _e, _pl, pack_g, _g in chunks]
+        feed = self._feed(None, glob)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev)
             sh = stream.cuda_stream
             try:
                 # the local model: one gather launch of every tensor into its layout slot
-                ptr_h.numpy()[:] = [local[k].data_ptr() for k, _, _, _ in lay]
-                ptr_d.copy_(ptr_h, non_blocking=True)
-                na.check(L.fa_gather_rows(dl.data_ptr(), total, 1, 4, ptr_d.data_ptr(), segs.data_ptr(), len(lay), sh),
-                         "fa_gather_rows")
-                for j, (first, end, _pl, _pg, g) in enumerate(chunks):
-                    if h is not None:
-                        ap.wait(h, j)
-                    elif any(f.result() for f in futs[j]):  # a value the native pack refuses: copy in Python
-                        for k, _s, o, n in g:
-                            gh.numpy()[o : o + n] = glob[k].reshape(-1)
+                db.ptr_h.numpy()[:] = [local[k].data_ptr() for k, _, _, _ in lay]
+                db.ptr_d.copy_(db.ptr_h, non_blocking=True)
+                na.check(L.fa_gather_rows(dl.data_ptr(), total, 1, 4, db.ptr_d.data_ptr(), db.segs.data_ptr(), len(lay),
+                                          sh), "fa_gather_rows")
+                for j, c in enumerate(chunks):
+                    feed.wait(j)
+                    first, end = c.first, c.end
                     dg[first:end].copy_(gh[first:end], non_blocking=True)
-                    epi = _epilogue(self.op, dl[first:end], v_in[first:end], p["beta"], p["eta"], p["tau"], p["beta2"],
-                                    v_out=v_out[first:end])
+                    epi = aggregator._epilogue(self.op, dl[first:end], v_in[first:end], p["beta"], p["eta"], p["tau"],
+                                               p["beta2"], v_out=v_out[first:end])
                     out = dout[first:end].data_ptr()
                     na.check(L.fa_opt_apply(prec, ctypes.byref(epi), dl[first:end].data_ptr(), dg[first:end].data_ptr(),
                                             end - first, None if prec == na.PREC_F64 else out,
                                             out if prec == na.PREC_F64 else None, sh), "fa_opt_apply")
             except BaseException:
-                if h is not None:
-                    ap.end(h)
-                else:
-                    for fg in futs:
-                        for f in fg:
-                            f.cancel()
-                    concurrent.futures.wait([f for fg in futs for f in fg])
-                stream.synchronize()
+                feed.abort(stream)
                 raise
-            if h is not None:
-                ap.end(h)
+            feed.end()
             done = torch.cuda.Event()
             done.record(stream)
         self._h2d_done = done
-        self.v, self._v_next = v_out, v_in
+        self.v.flip()
         # fresh result buffer per call: the returned tensors must not be overwritten by the next
-        res = dout
-        self._devbuf = db[:3] + (torch.empty(total, dtype=tdt, device=dev),) + db[4:]
-        return {k: res[o : o + n].view(s) for k, s, o, n in lay}
-
-    def _staging(self, lay, total, tdt, dev):
-        """Pinned staging for this layout, reused across calls (zeroed once: only the segments
-        are ever written, so the alignment gaps stay zero)."""
-        if getattr(self, "_stage", None) is None:
-            lh = torch.zeros(total, dtype=torch.float32, pin_memory=True)
-            gh = torch.zeros(total, dtype=tdt, pin_memory=True)
-            oh = None if self.zero_copy else torch.empty(total, dtype=tdt, pin_memory=True)
-            gdt = np.float64 if tdt == torch.float64 else np.float32
-            self._stage = (lh, gh, oh, _DictPack(lay, np.float32, lh.data_ptr()), _DictPack(lay, gdt, gh.data_ptr()))
-        return self._stage
+        db.dout = torch.empty(total, dtype=tdt, device=dev)
+        return {k: dout[o : o + n].view(s) for k, s, o, n in lay}

@@ -151,7 +151,8 @@ def test_server_optimizer_restore_refuses_a_foreign_v_t(cuda):
 def test_fused_round_refused_keeps_optimizer_state(cuda, monkeypatch):
     """A fused step whose launch is refused (here: reduce_stack raising before it queues anything)
     leaves the double-buffered state on the pair it had, so the rounds after it still match the
-    reference (ServerOptimizer.swap_buffers / unswap)."""
+    reference: the step only fetches its buffers (ServerOptimizer.step_buffers) and the state
+    advances to the pair it wrote (advance: DoubleBuffer.flip) after the launch call returned."""
     from flearn_amd import aggregator
 
     name = next(n for n in ROUND_CASES if Golden(n).meta["op"] == "avgm")
@@ -383,6 +384,74 @@ def test_column_window(col_begin, cuda):
     part = torch.empty(ncols, dtype=torch.float64, device=cuda)
     agg.reduce_stack(x, w, na.MODE_W32_DIV64, float(n), col_begin=col_begin, n_cols=ncols, out64=part)
     assert torch.equal(part, full[col_begin : col_begin + ncols])
+
+
+@pytest.mark.parametrize("bad", ["n_clients", "weights", "strided"])
+@pytest.mark.parametrize("kind", ["f64", "i64"])
+def test_eight_byte_reduce_refuses_what_the_launch_cannot_bound(kind, bad, cuda):
+    """reduce_stack_f64 / _i64 with more clients than rows, fewer weights than clients or a
+    column-strided stack raise before anything is queued (the launch layer knows neither the row
+    count nor the strides: it would read past the stack); the valid call on the same tensors
+    then equals the oracle."""
+    rng = np.random.default_rng(5)
+    n, p = 3, 64
+    if kind == "f64":
+        fn, xs, w = agg.reduce_stack_f64, rng.standard_normal((n, 2 * p)), rng.uniform(0.5, 2.0, n + 1)
+    else:
+        fn, xs = agg.reduce_stack_i64, rng.integers(-(2**40), 2**40, (n, 2 * p), dtype=np.int64)
+        w = rng.integers(1, 600, n + 1).astype(np.int64)
+    big, wd = torch.from_numpy(xs).to(cuda), torch.from_numpy(w).to(cuda)
+    stack = big[:, :p]  # a row-strided window: valid
+    denom = float(w[:n].sum())
+    out = torch.full((p,), -7.0, dtype=torch.float64, device=cuda)
+    with pytest.raises(ValueError):
+        if bad == "n_clients":
+            fn(stack, wd, denom, out, n + 1)
+        elif bad == "weights":
+            fn(stack, wd[: n - 1], denom, out)
+        else:
+            fn(big[:, ::2], wd, denom, out)
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all())
+    fn(stack, wd, denom, out)
+    assert bitwise_equal(out.cpu().numpy(), oracle.c_reduce(kind, xs[:, :p], w[:n], denom))
+
+
+@pytest.mark.parametrize("bad,exc", [("short", ValueError), ("dtype", TypeError)])
+@pytest.mark.parametrize("entry", ["apply_update", "apply_dyn"])
+def test_standalone_updates_refuse_a_bad_output(entry, bad, exc, cuda):
+    """apply_update / apply_dyn with an output of 60 elements for 64, or of the wrong dtype, raise
+    before anything is queued (the launch layer cannot know an output's size: it would write past
+    its end) and leave the state alone; the valid call on the same tensors then equals the oracle."""
+    p = 64
+    g = torch.rand(p, dtype=torch.float64, device=cuda)
+    local = torch.rand(p, device=cuda)  # w_local (apply_update) / h (apply_dyn)
+    state = torch.rand(p, dtype=torch.float64, device=cuda)  # v_t / theta
+    g_h, local_h, state_h = g.cpu().numpy(), local.cpu().numpy().copy(), state.cpu().numpy().copy()
+    if entry == "apply_update":
+        def call(**out):
+            agg.apply_update(na.OP_BY_NAME["adagrad"], local, g, state, **out)
+    else:
+        def call(**out):
+            agg.apply_dyn(g, local, state, 9, 0.05, **out)
+    for name, good_dt, bad_dt in (("out64", torch.float64, torch.float32), ("out32", torch.float32, torch.float64)):
+        wrong = torch.full((60,), -7.0, dtype=good_dt, device=cuda) if bad == "short" else \
+            torch.full((p,), -7.0, dtype=bad_dt, device=cuda)
+        with pytest.raises(exc):
+            call(**{name: wrong})
+        torch.cuda.synchronize()
+        assert bool((wrong == -7.0).all())
+        assert bitwise_equal(local.cpu().numpy(), local_h) and bitwise_equal(state.cpu().numpy(), state_h)
+    out64 = torch.empty(p, dtype=torch.float64, device=cuda)
+    out32 = torch.empty(p, dtype=torch.float32, device=cuda)
+    call(out64=out64, out32=out32)
+    if entry == "apply_update":
+        want = oracle.c_update("adagrad", g_h, local_h, state_h)
+    else:
+        want = oracle.c_update_dyn(g_h, local_h, state_h, 9, alpha=0.05)
+        assert bitwise_equal(local.cpu().numpy(), local_h)
+    assert bitwise_equal(out64.cpu().numpy(), want) and bitwise_equal(out32.cpu().numpy(), want.astype(np.float32))
+    assert bitwise_equal(state.cpu().numpy(), state_h)
 
 
 @pytest.mark.parametrize("mode", [na.MODE_W32_DIV64, na.MODE_W32_DIV32, na.MODE_W64])

@@ -456,3 +456,139 @@ def test_slab_stack_detection():
     assert stack_of(mixed)[2] is None
     other = [{"a": c["a"].clone(), "b": c["b"].clone(), "n": c["n"]} for c in sd]  # separate allocations
     assert stack_of(other)[2] is None
+
+
+# ---------------------------------------------------------------------------------------------
+# double-buffered state: one type behind PingPong, ServerOptimizer, DynState and DeviceUpdater
+# ---------------------------------------------------------------------------------------------
+
+
+def _shares_bytes(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def test_double_buffer_allocates_its_twin_lazily_and_flips(monkeypatch):
+    from flearn_amd.dist import DoubleBuffer
+
+    made = []
+    real = torch.empty_like
+    monkeypatch.setattr(torch, "empty_like", lambda t, *a, **k: made.append(t) or real(t, *a, **k))
+    first = torch.arange(6, dtype=torch.float64)
+    buf = DoubleBuffer(first)
+    assert buf.cur is first and buf.index == 0 and buf[0] is first
+    assert made == []  # an in-place user never pays for the second buffer
+    other = buf.other
+    assert len(made) == 1 and buf.other is other and len(made) == 1
+    assert other.shape == first.shape and other.dtype == first.dtype and not _shares_bytes(first, other)
+    assert buf[1] is other
+    buf.flip()
+    assert buf.cur is other and buf.other is first and buf.index == 1 and buf[0] is first and buf[1] is other
+    assert not _shares_bytes(buf.cur, buf.other)
+    buf.flip()
+    assert buf.cur is first and buf.other is other and buf.index == 0 and len(made) == 1
+
+
+def test_pingpong_window_out_and_flip():
+    from flearn_amd.dist import PingPong
+
+    prev, v = torch.arange(8, dtype=torch.float32), torch.arange(8, dtype=torch.float64)
+    st = PingPong(prev, v)
+    assert st.cur == 0 and st.prev[0] is prev and st.v[st.cur] is v
+    out0, v1 = st.out, st.v[1]
+    assert out0 is st.prev[1] and out0.shape == prev.shape and out0.dtype == prev.dtype
+    assert not _shares_bytes(out0, prev) and not _shares_bytes(v1, v)
+    p, vi, vo = st.window(2, 3)
+    assert p.data_ptr() == prev[2:5].data_ptr() and vi.data_ptr() == v[2:5].data_ptr()
+    assert vo.data_ptr() == v1[2:5].data_ptr() and p.numel() == vi.numel() == vo.numel() == 3
+    st.flip()
+    assert st.cur == 1 and st.out is prev and st.v[st.cur] is v1 and st.prev[1] is out0
+    p, vi, vo = st.window(0, 8)
+    assert p.data_ptr() == out0.data_ptr() and vi.data_ptr() == v1.data_ptr() and vo.data_ptr() == v.data_ptr()
+    st.flip()
+    assert st.cur == 0 and st.out is out0 and st.v[st.cur] is v
+
+
+def _two_cpu_shards():
+    from flearn_amd.bucket import Shard
+
+    rng = np.random.default_rng(11)
+    model = {"a": rng.standard_normal((10, 10)).astype(np.float32), "b": rng.standard_normal(7).astype(np.float32)}
+    plan = make_plan([1.0, 1.0], [model, model])
+    cpu = torch.device("cpu")
+    return model, plan, [Shard(0, cpu, 0, 64), Shard(1, cpu, 64, plan.f32.stride)]  # the cut splits key "a"
+
+
+def _assert_same(got: dict, want: dict):
+    assert set(got) == set(want)
+    for k in want:
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), k
+
+
+def test_server_optimizer_state_advances_only_when_told():
+    """A fused step's buffers (prev, v, prev_out, v_out) per shard: writing the output pair changes
+    nothing state_dict() shows until advance(), which is what a refused launch relies on."""
+    from flearn_amd.aggregator import ServerOptimizer
+
+    model, plan, shards = _two_cpu_shards()
+    v0 = {k: np.abs(x).astype(np.float64) for k, x in model.items()}
+    opt = ServerOptimizer("avgm")
+    opt.load_state({"w_glob": model, "v_t": v0})
+    assert opt.prepare(plan, shards)
+    for sh in shards:
+        prev, v, prev_o, v_o = opt.step_buffers(sh)
+        assert prev.numel() == v.numel() == prev_o.numel() == v_o.numel() == sh.width
+        assert prev_o.dtype == prev.dtype == torch.float32 and v_o.dtype == v.dtype == torch.float64
+        assert not _shares_bytes(prev, prev_o) and not _shares_bytes(v, v_o)
+        prev_o.copy_(prev + 1)
+        v_o.copy_(v * 2)
+    sd = opt.state_dict()
+    _assert_same(sd["w_glob"], model)
+    _assert_same(sd["v_t"], v0)
+    _assert_same(opt.v_t(), v0)
+    for sh in shards:
+        opt.advance(sh)
+    sd = opt.state_dict()
+    _assert_same(sd["w_glob"], {k: x + np.float32(1) for k, x in model.items()})
+    _assert_same(sd["v_t"], {k: x * 2 for k, x in v0.items()})
+    for sh in shards:  # the next step writes over the pair the last one read
+        prev, v, prev_o, v_o = opt.step_buffers(sh)
+        assert not _shares_bytes(prev, prev_o) and not _shares_bytes(v, v_o)
+    opt.init_global(model)  # a rebuilt state builds new buffers
+    assert opt.prepare(plan, shards)
+    _assert_same(opt.state_dict()["w_glob"], model)
+    _assert_same(opt.v_t(), {k: np.zeros_like(x) for k, x in v0.items()})
+
+
+def test_dyn_state_theta_advances_only_after_the_launch_returned(monkeypatch):
+    """DynState.step with the launch replaced: a refused one leaves theta_host() on the loaded
+    values, one that returned shows what it wrote into v_out; h is handed over in place."""
+    from flearn_amd import aggregator
+    from flearn_amd.aggregator import DynState
+
+    model, plan, shards = _two_cpu_shards()
+    dyn = DynState({k: x.copy() for k, x in model.items()})
+    assert dyn.prepare(plan, shards)
+    seen = []
+
+    def launch(stack, w, mode, denom, *, out32, out64, op, v, v_out, h, alpha, refuse=False):
+        assert op == na.OP_DYN and out64 is v_out and out32 is None and not _shares_bytes(v, v_out)
+        assert h.dtype == torch.float32 and v.dtype == torch.float64 and h.numel() == v.numel() == v_out.numel()
+        seen.append(h)
+        if refuse:
+            raise ValueError("refused launch")
+        v_out.copy_(v + 1)
+
+    theta0 = {k: x.astype(np.float64) for k, x in model.items()}
+    nm = plan.f32.numerics
+    monkeypatch.setattr(aggregator, "reduce_stack", lambda *a, **k: launch(*a, refuse=True, **k))
+    for sh in shards:
+        with pytest.raises(ValueError, match="refused launch"):
+            dyn.step(None, sh, None, None, nm, True)
+    _assert_same(dyn.theta_host(), theta0)
+    monkeypatch.setattr(aggregator, "reduce_stack", launch)
+    outs = [dyn.step(None, sh, None, None, nm, True) for sh in shards]
+    assert [o.numel() for o in outs] == [sh.width for sh in shards]
+    _assert_same(dyn.theta_host(), {k: x + 1 for k, x in theta0.items()})
+    assert all(seen[i] is seen[i + 2] for i in range(2))  # h: the same array every round

@@ -12,7 +12,7 @@ Priority also lets the gather's small kernels be dispatched ahead of the reduce'
 suits work on the step's critical path.
 
 The push gathers' pusher stream (both forms): its push kernels or own copies run beside the next
-stripe's reduce.  The copy-engine legs' streams stay at normal priority (flearn_amd.dist.peer_stream).
+stripe's reduce.  The copy-engine legs' streams stay at normal priority (flearn_amd.push.peer_stream).
 Round 5 saw wrong buckets with the copy-engine push's streams at high priority; round 6 found the
 cause — device-side cross-queue event waits that let copies start before their reduce finished,
 with several processes' streams on queues of their own — and removed the copy-engine push's

@@ -48,6 +48,7 @@ def _worker(rank, world, port, modes, priorities, steps, reps, out_path, dma_ord
     from flearn_amd import _native as na
     from flearn_amd import aggregator as agg
     from flearn_amd import dist as fd
+    from flearn_amd import push as fp
     from flearn_amd.dist import ShardedReducer, ShardPlan, StripeModel, hip_reduce_fn, plan_shards, plan_stripes
 
     torch.cuda.set_device(0)
@@ -171,18 +172,18 @@ def _worker(rank, world, port, modes, priorities, steps, reps, out_path, dma_ord
         return ok
 
     try:
-        product = (fd.side_stream, fd.peer_stream)
+        product = (fp.side_stream, fp.peer_stream)
         for prio in priorities:
-            if prio == "product":  # the streams as flearn_amd.dist creates them
-                fd.side_stream, fd.peer_stream = product
+            if prio == "product":  # the streams as flearn_amd.push creates them
+                fp.side_stream, fp.peer_stream = product
             else:  # "high": pusher and legs; "hipusher" / "hipeers": only that one at high priority
                 hi, lo = (lambda dev: torch.cuda.Stream(dev, priority=-1)), (lambda dev: torch.cuda.Stream(dev, priority=0))
-                fd.side_stream = hi if prio in ("high", "hipusher") else lo
-                fd.peer_stream = hi if prio in ("high", "hipeers") else lo
+                fp.side_stream = hi if prio in ("high", "hipusher") else lo
+                fp.peer_stream = hi if prio in ("high", "hipeers") else lo
             for rep in range(reps):
                 for mode in modes:
                     for order in (dma_orders if mode == "dma" else kernel_orders):
-                        fd._PUSH_ORDER = order if order != "-" else "auto"
+                        fp._PUSH_ORDER = order if order != "-" else "auto"
                         for fen in fences:
                             if compute == "created":  # the whole job on a created compute stream
                                 with torch.cuda.stream(torch.cuda.Stream(cuda)):
@@ -198,8 +199,8 @@ def _worker(rank, world, port, modes, priorities, steps, reps, out_path, dma_ord
                                             "bad_steps": [{"step": 0, "bad": -1}]})
                 dist.barrier()
             fd.shutdown_push()
-        fd.side_stream, fd.peer_stream = product
-        fd._PUSH_ORDER = "auto"
+        fp.side_stream, fp.peer_stream = product
+        fp._PUSH_ORDER = "auto"
         gathered = [None] * world
         dist.all_gather_object(gathered, results)
         if rank == 0:

@@ -1,12 +1,13 @@
-"""The push gather's receive pool (flearn_amd.dist._RecvPool) on CPU, gloo world 2.
+"""The push gather's receive pool (flearn_amd.push._RecvPool) on CPU, gloo world 2.
 
 The GPU parts are stubbed (the bucket allocation, `_map_peers`' IPC export / import, the unmaps),
 the collective protocol is real: buckets are mapped once and handed out again, the first free
 slot that fits is reused, a slot in use is never handed out twice, a larger request retires the
 free buckets (every peer unmaps, barrier, park) before it maps a new one, ranks whose pools
 disagree all raise, `shutdown_push` empties the pools with every import closed before any bucket
-is parked, the next pool re-exports a parked bucket, and a destroyed and re-created default group
-maps its buckets afresh.  `test_parked_buckets_stay_within_the_cap` runs the real DeviceBuffer and
+is parked, the next pool re-exports a parked bucket, a destroyed and re-created default group
+maps its buckets afresh, and a take on a device the transport does not accept is refused on every
+rank together with nothing allocated.  `test_parked_buckets_stay_within_the_cap` runs the real DeviceBuffer and
 `_map_peers` over a shared-memory stand-in for HIP IPC: growing then shrinking requests keep the
 parked bytes within the cap, and every mapping is token-checked (a wrong one refused)."""
 import os
@@ -63,10 +64,10 @@ def _install_stubs(fd, events):
             parked.append(self)
             events.append(("park", self.id))
 
-    def fake_map(pg, full):
-        dist.barrier(group=pg.group)  # collective like the real one
+    def fake_map(ctx, full):
+        dist.barrier(group=ctx.group)  # collective like the real one
         events.append(("map", full.numel()))
-        return [1000 + full.numel()], [full.data_ptr()] * pg.world, []
+        return [1000 + full.numel()], [full.data_ptr()] * ctx.world, []
 
     fd.DeviceBuffer = FakeBuf
     fd._map_peers = fake_map
@@ -83,7 +84,7 @@ def _cols(want):  # the pool's request: ALIGN-rounded (DeviceBuffer.get applies 
 
 
 def _worker(rank, world, init):
-    from flearn_amd import dist as fd
+    from flearn_amd import push as fd
 
     dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
     ev = []
@@ -118,10 +119,10 @@ def _worker(rank, world, init):
         pool.give(k)
         # rank 1 holds slot 0 while rank 0 does not: the picks differ, every rank raises
         if rank == 1:
-            pool.slots[0][4] = True
+            pool.slots[0].busy = True
         with pytest.raises(RuntimeError, match="disagree"):
             pool.take(pg, 10)
-        pool.slots[0][4] = False
+        pool.slots[0].busy = False
         dist.barrier()
         # shutdown: every import closed (and a barrier) before anything is parked; the pools hold
         # nothing, the parked buckets wait for reuse
@@ -235,11 +236,8 @@ class _ShmIpc:
         return b""
 
 
-def _cap_worker(rank, world, init):
-    from flearn_amd import dist as fd
-
-    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
-    ev = []
+def _install_shm(fd, ev):
+    """The real DeviceBuffer and _map_peers over the shared-memory stand-in."""
     ipc = _ShmIpc(ev)
     fd._IPC = ipc
     fd._RecvPool._pools.clear()
@@ -255,6 +253,15 @@ def _cap_worker(rank, world, init):
         self.ptr = self._alloc()
 
     fd.DeviceBuffer.__init__ = init_buf
+    return ipc
+
+
+def _cap_worker(rank, world, init):
+    from flearn_amd import push as fd
+
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
+    ev = []
+    ipc = _install_shm(fd, ev)
     try:
         pg = types.SimpleNamespace(world=world, rank=rank, group=None, nccl=False, device=torch.device("cpu"))
         pool = fd._RecvPool.get("cpu", None)
@@ -303,6 +310,48 @@ def _cap_worker(rank, world, init):
 def test_parked_buckets_stay_within_the_cap():
     init = "file://" + os.path.join(tempfile.mkdtemp(prefix="fa_cap_"), "pg")
     mp.spawn(_cap_worker, args=(2, init), nprocs=2, join=True)
+
+
+def _refusal_worker(rank, world, init):
+    from flearn_amd import push as fd
+
+    dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
+    ev = []
+    ipc = _install_shm(fd, ev)
+    try:
+        ctx = fd.PeerContext.of(None, "cpu")
+        assert (ctx.world, ctx.rank, ctx.nccl) == (world, rank, False)
+        # a device the transport does not accept (the stand-in maps host memory only): every rank
+        # is refused together, after the same collectives as a mapping, with nothing allocated
+        refused = fd._RecvPool.get("cuda:0", None)
+        with pytest.raises(RuntimeError, match="could not map"):
+            refused.take(ctx, 1000)
+        assert refused.slots == [] and fd._RecvPool.bytes_held() == 0
+        assert fd.DeviceBuffer.parked_bytes() == 0 and not ipc.own and not ev
+        # no peer is left inside a collective: the next take, on an accepted device, maps
+        pool = fd._RecvPool.get("cpu", None)
+        i, buf, dsts = pool.take(ctx, 1000)
+        assert i == 0 and buf.numel() >= 1000 and len(dsts) == world
+        assert sum(1 for e in ev if e[0] == "token_read") == world - 1
+        pool.give(i)
+        # a rank that refuses alone takes its peers with it instead of leaving them in a collective
+        if rank == 1:
+            ipc.accepts = lambda device: False
+        with pytest.raises(RuntimeError, match="could not map"):
+            pool.take(ctx, 5000)
+        assert pool.slots == [] and not ipc.attached
+        fd.shutdown_push()
+        assert fd._RecvPool.bytes_held() == 0 and not fd._RecvPool._pools
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+        for a in list(ipc.own):
+            ipc.release(a)
+
+
+def test_refusal_on_a_device_the_transport_does_not_accept():
+    init = "file://" + os.path.join(tempfile.mkdtemp(prefix="fa_refuse_"), "pg")
+    mp.spawn(_refusal_worker, args=(2, init), nprocs=2, join=True)
 
 
 def test_size_classes():

@@ -1,5 +1,5 @@
 """Diagnose the push gather's stale IPC imports: the export -> map -> unmap ->
-free -> re-export sequence of flearn_amd.dist, repeated, with every handle, exported range and
+free -> re-export sequence of flearn_amd.push, repeated, with every handle, exported range and
 mapping logged.
 
     python tools/ipc_probe.py --world 3 --iters 40 --alloc torch --after-unmap none --free del \

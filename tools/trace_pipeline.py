@@ -36,6 +36,7 @@ def run(a):
     from flearn_amd import aggregator as agg
     from flearn_amd import dist as fd
     from flearn_amd import layouts
+    from flearn_amd import push as fp
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -52,7 +53,7 @@ def run(a):
         agg.fill_uniform(stack, seed=2024)
         w = torch.ones(n, dtype=torch.float32, device=dev)
         push = {"rccl": False, "push": True, "push_dma": "dma"}[a.gather]
-        fd._PUSH_ORDER = a.order  # auto (the product), host, or producer (a device-side event wait)
+        fp._PUSH_ORDER = a.order  # auto (the product), host, or producer (a device-side event wait)
         red = fd.ShardedReducer(plan, fd.hip_reduce_fn(stack, w, na.MODE_W32_DIV64, float(n)), dev, gather=True,
                                 push=push)
         if red.pusher is not None and a.pusher_stream != "default":
@@ -127,7 +128,7 @@ def main():
     ap.add_argument("--gather", default="push", choices=["rccl", "push", "push_dma"])
     ap.add_argument("--stripes", type=int, default=4)
     ap.add_argument("--order", default="auto", choices=["auto", "host", "producer"],
-                    help="how each stripe's push follows its reduce (flearn_amd.dist._PUSH_ORDER; auto: the "
+                    help="how each stripe's push follows its reduce (flearn_amd.push._PUSH_ORDER; auto: the "
                          "product's — producer for the kernel push, host for the copy-engine push)")
     ap.add_argument("--clients", type=int, default=100)
     ap.add_argument("--cols", type=int, default=0, help="columns of the stack (0: NS, 100 x ResNet-50; "

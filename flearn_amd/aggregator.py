@@ -1,7 +1,7 @@
 """Device aggregation engine behind Strategy.server_ensemble.
 
 `Aggregator.ensemble(agg_weight_lst, w_local_lst, key_lst)` is the MI355X replacement for
-flearn/common/strategy/strategy.py:102-130: plan the buckets (bucket.py), copy the uploads into
+flearn/common/strategy/strategy.py:102-130: plan the buckets (bucketplan.py), copy the uploads into
 HBM, run ONE fused reduce launch per bucket kind on torch's current stream, and hand back a
 fresh dict with the reference's value types.
 
@@ -17,15 +17,17 @@ tensors directly and are what bench.py and the multi-GPU path use.
 from __future__ import annotations
 
 import ctypes
+import itertools
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _native as na
-from .bucket import (FMT, SMALL_BYTES, TORCH_DTYPE, AsyncPack, BucketPlan, NativeRows, Packer, RowTable, Shard,
-                     make_plan, rank_width)
+from .bucketplan import SMALL_BYTES, TORCH_DTYPE, BucketPlan, Shard, _as_list, make_plan, rank_width
 from .dist import DoubleBuffer, gather_columns
+from .packer import AsyncPack, NativeRows, Packer, piece_columns
+from .rowtable import RowTable
 from .semantics import KIND_F16, KIND_F32, KIND_F64, KIND_I64, Numerics
 from .wire import wire_row
 
@@ -681,6 +683,16 @@ class DynState:
 OUTPUTS = ("reference", "float32", "device")
 
 
+def chain_table(pieces, host_ptr: int, row_bytes: int, bounds) -> np.ndarray:
+    """AsyncPack's job table of a chained small round (Aggregator._small_chain): clients
+    [bounds[k], bounds[k + 1]) are part k, packed as chunk k, and client i of part k goes to row
+    i + k of the staging at host_ptr — each part leaves a row free for the partial sum before it."""
+    part = np.repeat(np.arange(len(bounds) - 1), np.diff(bounds))[:, None]  # per client
+    client = np.arange(bounds[-1])[:, None]
+    source, base, pitch, off = piece_columns(pieces, ((host_ptr, row_bytes),))
+    return AsyncPack.table(src=client, dst=base + (client + part) * pitch + off, chunk=part, **source)
+
+
 class _SmallChain(NamedTuple):
     """The fp32 bucket of a small zero-copy round as chained launches (Aggregator._small_chain)."""
     pack: AsyncPack  # native threads pack part k's clients as its chunk k
@@ -730,7 +742,7 @@ class Aggregator:
     #: process, bit-equal (tools/prof_host_c1.py --ab, profiles/r03/c1_zc/); False = copy engines
     small_zero_copy = True
     #: the zero-copy fp32 bucket of a small round may be summed in this many chained launches
-    #: (client parts, each launched as soon as native threads have packed it: bucket.AsyncPack);
+    #: (client parts, each launched as soon as native threads have packed it: packer.AsyncPack);
     #: 1 = one native pack on the calling thread, one launch.  At flearn's config 1 every extra
     #: launch costs more than the overlap saves: 1 / 2 / 3 / 4 launches 113.5 / 120.3 / 127.4 /
     #: 135.7 us per server call, numpy 142 us (tools/prof_host_c1.py --parts, profiles/r04/c1_parts/)
@@ -894,8 +906,7 @@ class Aggregator:
                 args = (stack.data_ptr(), g.stride, n, w.data_ptr(), float(nm.denom), 0, g.stride, dout.data_ptr())
             out = [(s.key, s.offset, s.numel, s.shape) for s in g.segments]
             buckets.append(_SmallBucket(nat, host, stack, w, dout, hout, hout.numpy(), fn, args, out, chain))
-        g32 = plan.groups.get(KIND_F32)
-        wsig = (tuple((s.key, s.shape, s.offset) for s in g32.segments) + (g32.stride,)) if g32 is not None else None
+        wsig = plan.f32.row_layout if plan.f32 is not None else None
         rec = plan.memo[key] = _SmallRecord(tuple(buckets), na.load_pyhost().fa_py_pack_rows, wsig)
         return rec
 
@@ -910,24 +921,11 @@ class Aggregator:
         fl32(1 * acc) = acc, so the chain of adds is the single launch's, bit for bit, and no
         launch writes a row it reads.  The parts are packed by native threads
         (AsyncPack chunk k = part k) and each launch waits only for its own part."""
-        base, rem = divmod(n, parts)
-        sizes = [base] * parts
-        for j in range(rem):  # the remainder goes to the last parts
-            sizes[parts - 1 - j] += 1
-        bounds = [0]
-        for s_ in sizes:
-            bounds.append(bounds[-1] + s_)
+        base, rem = divmod(n, parts)  # the remainder goes to the last parts
+        bounds = [0, *itertools.accumulate(base + (k >= parts - rem) for k in range(parts))]
         row = g.stride * 4
         hp = host.data_ptr()
-        rows = []
-        for k in range(parts):
-            for i in range(bounds[k], bounds[k + 1]):
-                for s, a, b, _sh, d in pieces:
-                    it = s.src_dtype.itemsize
-                    rows.append((i, s.numel * it, FMT[s.src_dtype], hp + (i + k) * row + d * it, k, a * it,
-                                 (b - a) * it))
-        keys = tuple(s.key for s, *_ in pieces) * n
-        ap = AsyncPack(keys, np.array(rows, dtype=np.int64).reshape(-1, 7), parts)
+        ap = AsyncPack(tuple(p.segment.key for p in pieces) * n, chain_table(pieces, hp, row, bounds), parts)
         one = torch.ones(1, dtype=torch.float32, device=dev)
         args, ws = [], []
         for k in range(parts):
@@ -958,7 +956,7 @@ class Aggregator:
         if rec is None:
             return None
         buckets = rec.buckets
-        lst = w_local_lst if type(w_local_lst) is list else list(w_local_lst)
+        lst = _as_list(w_local_lst)
         # decoded by the wire codec into pinned rows of this layout: the general path DMAs them as is
         if rec.wsig is not None and wire_row(lst[0], rec.wsig) is not None:
             return None

@@ -99,7 +99,8 @@ def fp32_tensors(layout) -> int:
 
 
 def padded_f32_stride(layout, align=64) -> int:
-    """Row length of the f32 bucket for this layout (bucket.py's ALIGN padding per key)."""
+    """Row length of the f32 bucket for this layout (bucketplan.py's ALIGN padding per key)."""
+    # bucketplan.padded_span's rule, written out: this module stays numpy-only and that one imports torch
     return sum(-(-max(math.prod(s), 1) // align) * align for _, s, t in layout if t == "f32")
 
 

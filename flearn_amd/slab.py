@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .bucket import make_plan
+from .bucketplan import make_plan
 from .semantics import KIND_F32
 
 

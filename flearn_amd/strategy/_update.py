@@ -10,7 +10,6 @@ from __future__ import annotations
 import concurrent.futures
 import ctypes
 import math
-import os
 import time
 from dataclasses import dataclass, field
 from typing import NamedTuple
@@ -20,10 +19,10 @@ import torch
 
 from .. import _native as na
 from .. import aggregator  # its _epilogue / apply_update are called through the module (tests patch them there)
-from ..bucket import ALIGN, AsyncPack
+from ..bucketplan import FMT, padded_span
 from ..dist import DoubleBuffer
+from ..packer import AsyncPack, NativeRows, pack_threads
 
-_FMT = {np.dtype(np.float32): ord("f"), np.dtype(np.float64): ord("d")}
 _F32 = np.dtype(np.float32)
 _DEV_GLOB = (np.dtype(np.float64), _F32)  # w_glob dtypes the device path takes
 _PART_BYTES = 16 << 20  # host copies are split into parts of about this size, one per pool task
@@ -35,11 +34,7 @@ def _pool() -> concurrent.futures.ThreadPoolExecutor:
     if _POOL is None:
         # the pack is host-memory copies (the GIL released): as many threads as the process may
         # use, up to 16 (the GPU box's CPU share per GPU)
-        try:
-            cpus = len(os.sched_getaffinity(0))
-        except (AttributeError, OSError):
-            cpus = os.cpu_count() or 8
-        _POOL = concurrent.futures.ThreadPoolExecutor(max(4, min(16, cpus)), thread_name_prefix="fa-update")
+        _POOL = concurrent.futures.ThreadPoolExecutor(pack_threads(), thread_name_prefix="fa-update")
     return _POOL
 
 
@@ -57,7 +52,7 @@ class _DictPack:
 
     def __init__(self, lay, dtype, dst_ptr, part_bytes=_PART_BYTES):
         self.fn = na.load_pyhost().fa_py_pack_rows
-        item, fmt = np.dtype(dtype).itemsize, _FMT[np.dtype(dtype)]
+        item, fmt = np.dtype(dtype).itemsize, FMT[np.dtype(dtype)]
         parts, cur, size = [], [], 0
         for k, _s, o, n in lay:
             cur.append((k, n, o))
@@ -68,16 +63,11 @@ class _DictPack:
         if cur:
             parts.append(cur)
         self.parts = []
-        for part in parts:  # desc table: total, src_lo, nbytes, fmt, dst_base, dst_row, dst_off; skip
-            m = len(part)
-            desc = np.zeros(7 * m + 1, dtype=np.int64)
+        for part in parts:  # whole values into the one staging row, which is not skipped
             nb = np.array([n for _, n, _ in part], dtype=np.int64) * item
-            desc[0:m] = nb
-            desc[2 * m:3 * m] = nb
-            desc[3 * m:4 * m] = fmt
-            desc[4 * m:5 * m] = dst_ptr
-            desc[6 * m:7 * m] = np.array([o for _, _, o in part], dtype=np.int64) * item
-            self.parts.append((tuple(k for k, _, _ in part), desc))
+            desc = NativeRows.table(value_bytes=nb, first_byte=0, nbytes=nb, fmt=fmt, dst_base=dst_ptr, dst_row=0,
+                                    dst_off=np.array([o for _, _, o in part], dtype=np.int64) * item)
+            self.parts.append((tuple(k for k, _, _ in part), np.append(desc, 0)))
 
     def tasks(self, d: dict):
         """The pack as pool tasks (one per part); each returns 0 on success."""
@@ -150,16 +140,17 @@ class _AsyncPack(AsyncPack):
 
     def __init__(self, chunks, lh_ptr, gh_ptr, gdtype):
         item = torch.empty((), dtype=gdtype).element_size()
-        gfmt = ord("d") if item == 8 else ord("f")
-        keys, rows = [], []
-        for j, (*_, slots) in enumerate(chunks):  # _Chunks, or any tuples that end in their slots
-            for k, _s, o, n in slots:
-                if lh_ptr is not None:
-                    keys.append(k)
-                    rows.append((0, n * 4, ord("f"), lh_ptr + o * 4, j, 0, n * 4))
-                keys.append(k)
-                rows.append((1, n * item, gfmt, gh_ptr + o * item, j, 0, n * item))
-        super().__init__(tuple(keys), np.array(rows, dtype=np.int64).reshape(-1, 7), len(chunks))
+        # the dicts copied from: (index in start()'s pair, staging address, itemsize, format class)
+        srcs = [(0, lh_ptr, 4, ord("f"))] if lh_ptr is not None else []
+        srcs.append((1, gh_ptr, item, ord("d") if item == 8 else ord("f")))
+        src, base, size, fmt = np.array(srcs, dtype=np.int64).T
+        # _Chunks, or any tuples that end in their slots: per slot its chunk, offset and elements
+        chunk, off, numel = np.array([(j, o, n) for j, (*_, slots) in enumerate(chunks) for _k, _s, o, n in slots],
+                                     dtype=np.int64).reshape(-1, 3).T[:, :, None]
+        rows = self.table(src=src, value_bytes=numel * size, fmt=fmt, dst=base + off * size, chunk=chunk,
+                          first_byte=0, nbytes=numel * size)
+        keys = tuple(k for *_, slots in chunks for k, *_ in slots for _ in srcs)
+        super().__init__(keys, rows, len(chunks))
 
     def start(self, local, glob):
         return super().start((local if local is not None else {}, glob))
@@ -252,7 +243,7 @@ class DeviceUpdater:
         for k, shape in sig:
             n = math.prod(shape) if shape else 1
             lay.append(_Slot(k, shape, off, n))
-            off += -(-max(n, 1) // ALIGN) * ALIGN
+            off += padded_span(n)
         self._lay_cache = (sig, lay, off)
         return lay, off
 

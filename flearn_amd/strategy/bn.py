@@ -3,7 +3,7 @@ name contains "bn" is excluded on both sides; the rest goes through the same dev
 from __future__ import annotations
 
 from .avg import AVG
-from ..bucket import select_keys
+from ..bucketplan import select_keys
 
 
 class BN(AVG):

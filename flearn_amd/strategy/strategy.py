@@ -32,7 +32,7 @@ from .._native import NativeError, NativeUnavailable
 _DEVICE_ERRORS = (NativeUnavailable, NativeError, torch.OutOfMemoryError, torch.AcceleratorError,
                   _dist.DistError)
 #: what bad client data raises — numpy's errors on the reference's arithmetic (shape/dtype/key
-#: mismatches, an empty list), the engine's own validation (bucket.py / semantics.py) and the
+#: mismatches, an empty list), the engine's own validation (bucketplan.py / semantics.py) and the
 #: deliberate refusals of unsupported client data (NotImplementedError): these take the
 #: reference's server_exception -> SystemExit route (avg.py:28-31).  Everything else — a plain
 #: RuntimeError from a gloo/c10d collective (timeout, dead peer), a device-placement error,

@@ -12,7 +12,7 @@ are copied once more into the aggregation input.
   *through* the base64 text, decoding only its small header pieces, and reports every array
   payload as a (decoded offset, length) range.  The fp32 arrays of an upload's ``params`` are
   then decoded by a thread pool straight into ONE pinned row laid out exactly as the
-  aggregation bucket (bucket.make_plan: key order, 64-element alignment), and handed back as
+  aggregation bucket (bucketplan.make_plan: key order, 64-element alignment), and handed back as
   numpy views of it — a plain dict of plain ndarrays, equal to what ``pickle.loads`` returns.
   When the engine later aggregates those uploads, the Packer recognises the rows and DMAs them
   to the GPU as they are (no pack copy).
@@ -32,16 +32,18 @@ import collections
 import ctypes
 import io
 import json
+import math
 import os
 import pickle
 import threading
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _native as na
-from .bucket import ALIGN
+from .bucketplan import layout_slots, layout_stride, padded_span, row_layout
 
 __all__ = ["BaseEncrypt", "Encrypt", "b64encode", "b64decode", "wire_row", "wire_device_stack",
            "release_device_staging"]
@@ -127,8 +129,6 @@ def b64encode(raw) -> str:
     L = na.load()
     mv = memoryview(raw).cast("B")
     if not _FILL_IN_PLACE:
-        import base64
-
         return base64.b64encode(mv).decode("ascii")
     n = mv.nbytes
     m = 4 * ((n + 2) // 3)
@@ -245,7 +245,22 @@ def restricted_loads(data) -> object:
 # ---------------------------------------------------------------------------------------------
 # pinned rows handed out by decode (weakly tracked, verified by address before reuse)
 # ---------------------------------------------------------------------------------------------
-_ROWS: dict[int, tuple] = {}
+class _Staged(NamedTuple):
+    """Where _DeviceStage.stage put a decoded row: slot `slot` of round `gen` of `stage`."""
+    stage: "_DeviceStage"
+    gen: int
+    slot: int
+
+
+class _RowEntry(NamedTuple):
+    """What the registry knows of one decoded params dict."""
+    row_ref: weakref.ref  # its pinned row (a _RowArray), weakly
+    layout: tuple  # the row's row_layout
+    staged: _Staged | None  # its device copy, when decode staged one
+    refs: tuple  # the arrays handed out, weakly, in layout order
+
+
+_ROWS: dict[int, _RowEntry] = {}
 # re-entrant: a row's weakref callback (_drop_entry) may run from the garbage collector while
 # this thread already holds the lock
 _ROWS_LOCK = threading.RLock()
@@ -260,7 +275,7 @@ class _RowArray(np.ndarray):
 def _register(params: dict, row_np: _RowArray, layout: tuple, staged=None):
     # the exact array objects handed out, weakly: wire_row then checks identity (an array that was
     # replaced is a different object; an array cannot move, so identity pins its address too)
-    refs = tuple(weakref.ref(params[k]) for k, _, _ in layout[:-1])
+    refs = tuple(weakref.ref(params[k]) for k, _, _ in layout_slots(layout))
     key = id(params)
     with _ROWS_LOCK:
         if len(_ROWS) > 4096:
@@ -270,17 +285,17 @@ def _register(params: dict, row_np: _RowArray, layout: tuple, staged=None):
                 _ROWS.pop(k, None)
         # the entry goes when its row dies (a params dict cannot be weakly referenced, so a dict
         # freed while its arrays live on leaves the entry behind: _live_entry drops it on lookup)
-        _ROWS[key] = (weakref.ref(row_np, lambda r, k=key: _drop_entry(k, r)), layout, staged, refs)
+        _ROWS[key] = _RowEntry(weakref.ref(row_np, lambda r, k=key: _drop_entry(k, r)), layout, staged, refs)
 
 
-def _entry_alive(ent) -> bool:
-    return ent[0]() is not None and all(r() is not None for r in ent[3])
+def _entry_alive(ent: _RowEntry) -> bool:
+    return ent.row_ref() is not None and all(r() is not None for r in ent.refs)
 
 
 def _drop_entry(key: int, row_ref) -> None:
     with _ROWS_LOCK:
         ent = _ROWS.get(key)
-        if ent is not None and ent[0] is row_ref:
+        if ent is not None and ent.row_ref is row_ref:
             del _ROWS[key]
 
 
@@ -297,7 +312,7 @@ def _live_entry(params: dict):
         if not _entry_alive(ent):
             del _ROWS[key]
             return None
-    for (k, _shape, _off), ref in zip(ent[1][:-1], ent[3]):
+    for (k, _shape, _off), ref in zip(layout_slots(ent.layout), ent.refs):
         if params.get(k) is not ref():
             with _ROWS_LOCK:
                 if _ROWS.get(key) is ent:
@@ -317,7 +332,7 @@ class _DeviceStage:
     H2D is left to do.  The copy is a snapshot taken at decode time."""
 
     def __init__(self, device: torch.device, layout: tuple):
-        self.device, self.layout, self.stride = device, layout, layout[-1]
+        self.device, self.layout, self.stride = device, layout, layout_stride(layout)
         self.buf = None
         self.cap = 0
         self.n = 0  # rows staged in the current round
@@ -345,7 +360,7 @@ class _DeviceStage:
                 self.done.record(self.stream)
         slot = self.n
         self.n += 1
-        return (self, self.gen, slot)
+        return _Staged(self, self.gen, slot)
 
     def take(self, n: int) -> torch.Tensor:
         """Hand the first n slots to the engine (its stream waits for the copies) and start a new
@@ -381,12 +396,12 @@ def wire_device_stack(params_list, layout: tuple, device):
     in list order, into slots 0..N-1 of the same round on `device` and still holds the decoder's
     arrays — else None (the caller then DMAs the pinned rows or packs)."""
     ents = [_live_entry(p) for p in params_list]
-    stages = {e[2][0] for e in ents if e is not None and e[2] is not None}
-    ok = bool(ents) and len(stages) == 1 and all(e is not None and e[2] is not None for e in ents)
+    stages = {e.staged.stage for e in ents if e is not None and e.staged is not None}
+    ok = bool(ents) and len(stages) == 1 and all(e is not None and e.staged is not None for e in ents)
     if ok:
-        st, gen = ents[0][2][0], ents[0][2][1]
+        st, gen, _slot = ents[0].staged
         ok = st.device == torch.device(device) and st.n == len(ents) and gen == st.gen
-        ok = ok and all(e[2] == (st, gen, i) and wire_row(p, layout) is not None
+        ok = ok and all(e.staged == (st, gen, i) and wire_row(p, layout) is not None
                         for i, (e, p) in enumerate(zip(ents, params_list)))
     if ok:
         return st.take(len(ents))
@@ -400,9 +415,9 @@ def wire_row(params: dict, layout: tuple):
     """The pinned row behind a decoded upload's params when its fp32 arrays are still the
     decoder's views laid out as `layout` ((key, shape, offset), ..., stride) — else None."""
     ent = _live_entry(params)
-    if ent is None or ent[1] != layout:
+    if ent is None or ent.layout != layout:
         return None
-    row_np = ent[0]()
+    row_np = ent.row_ref()
     return None if row_np is None else row_np._fa_tensor
 
 
@@ -411,24 +426,29 @@ def wire_row(params: dict, layout: tuple):
 # ---------------------------------------------------------------------------------------------
 
 
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= s
-    return n
+class _Template:
+    """The decode plan: everything decode_fast derives from a scanner manifest alone — the parsed
+    tree (read-only once planned), the fp32 row's plan and layout, the aux-buffer layout and the
+    payload ranges.  Uploads of one model with the same weight produce the same manifest text
+    (pickle lays the same dict out the same way), so a round of N uploads plans once instead of
+    N times; `build` then makes each upload's objects over its own row and aux buffer."""
 
+    __slots__ = ("tree", "row_plan", "row_nodes", "layout", "aux_size", "offs", "lens", "rel", "in_row")
 
-class _Decoder:
-    def __init__(self, L, ptr, n):
-        self.L, self.ptr, self.n = L, ptr, n
-        self.ranges = []  # (off, len, dst address)
-        self.aux_size = 0
+    def __init__(self, tree):
+        self.tree = tree
         self.row_plan = {}  # id(node) -> row offset (elements)
         self.row_nodes = []  # the planned manifest nodes, in layout order
-        self.row_built = {}  # id(node) -> the ndarray view build() made for it
+        self.layout = self._plan_row(tree)  # the pinned row's row_layout; None: no row
+        self.aux_size = 0
+        ranges = []  # per non-empty payload: (text offset, bytes, offset in its destination, is the row)
+        self._place(tree, ranges)
+        offs, lens, rel, in_row = zip(*ranges) if ranges else ((),) * 4
+        self.offs, self.lens, self.rel = (np.array(c, np.int64) for c in (offs, lens, rel))
+        self.in_row = np.array(in_row, bool)
 
-    # pass 1: find the upload's params dict and lay out its fp32 C-order arrays
-    def plan_row(self, tree):
+    def _plan_row(self, tree):
+        """Find the upload's params dict and lay out its fp32 C-order arrays as one row."""
         if not (isinstance(tree, dict) and "__d" in tree):
             return None
         params = None
@@ -437,48 +457,50 @@ class _Decoder:
                 params = v
         if params is None:
             return None
-        layout, stride = [], 0
+        slots, stride = [], 0
         for k, v in params.get("__d", params.get("__od")):
             if not (isinstance(k, str) and isinstance(v, dict) and "__nd" in v):
                 continue
             dt, shape, fortran, _off, _len, _ss = v["__nd"]
             if np.dtype(dt) != _F32 or (fortran and len(shape) > 1):
                 continue
-            numel = _numel(shape)
             self.row_plan[id(v)] = stride
             self.row_nodes.append(v)
-            layout.append((k, tuple(shape), stride))
-            stride += -(-max(numel, 1) // ALIGN) * ALIGN
-        if not layout:
-            return None
-        return params, tuple(layout) + (stride,)
+            slots.append((k, tuple(shape), stride))
+            stride += padded_span(math.prod(shape))
+        return row_layout(slots, stride) if slots else None
 
-    def aux(self, nbytes, align=16):
-        o = -(-self.aux_size // align) * align
-        self.aux_size = o + nbytes
-        return o
-
-    # pass 2: assign destinations
-    def assign(self, node):
+    def _place(self, node, ranges):
+        """One walk over the payload nodes: each gets its destination — its planned row slot,
+        else the next 16-byte aligned place of the aux buffer (node["_aux"]) — and its text range."""
         if isinstance(node, list):
             for x in node:
-                self.assign(x)
+                self._place(x, ranges)
         elif isinstance(node, dict):
             if "__nd" in node:
-                if id(node) not in self.row_plan:
-                    node["_aux"] = self.aux(node["__nd"][4])
+                o, ln = node["__nd"][3], node["__nd"][4]
             elif "__sc" in node:
-                node["_aux"] = self.aux(node["__sc"][2])
+                o, ln = node["__sc"][1], node["__sc"][2]
             elif "__b" in node:
-                node["_aux"] = self.aux(node["__b"][1])
+                o, ln = node["__b"]
             else:
                 for key in ("__t", "__d", "__od"):
                     if key in node:
-                        self.assign(node[key])
+                        self._place(node[key], ranges)
+                return
+            row = id(node) in self.row_plan
+            if row:
+                rel = 4 * self.row_plan[id(node)]
+            else:
+                rel = node["_aux"] = -(-self.aux_size // 16) * 16
+                self.aux_size = rel + ln
+            if ln:
+                ranges.append((o, ln, rel, row))
 
-    def build(self, node, row_np, aux_np):
+    def build(self, node, row_np, aux_np, built):
+        """The objects of one upload; built: id(node) -> the row view made for that planned node."""
         if isinstance(node, list):
-            return [self.build(x, row_np, aux_np) for x in node]
+            return [self.build(x, row_np, aux_np, built) for x in node]
         if not isinstance(node, dict):
             return node
         if "__nd" in node:
@@ -486,7 +508,7 @@ class _Decoder:
             dtype = np.dtype(dt)
             if "_aux" not in node:
                 o = self.row_plan[id(node)]
-                arr = self.row_built[id(node)] = row_np[o : o + _numel(shape)].view(np.ndarray).reshape(shape)
+                arr = built[id(node)] = row_np[o : o + math.prod(shape)].view(np.ndarray).reshape(shape)
                 return arr
             count = nbytes // dtype.itemsize if dtype.itemsize else 0
             flat = np.frombuffer(aux_np, dtype=dtype, count=count, offset=node["_aux"]) if count else np.empty(0, dtype)
@@ -503,32 +525,19 @@ class _Decoder:
         if "__f" in node:
             return float.fromhex(node["__f"])
         if "__t" in node:
-            return tuple(self.build(x, row_np, aux_np) for x in node["__t"])
+            return tuple(self.build(x, row_np, aux_np, built) for x in node["__t"])
         if "__dt" in node:
             return np.dtype(node["__dt"])
         if "__d" in node or "__od" in node:
             out = {} if "__d" in node else collections.OrderedDict()
             for k, v in node.get("__d", node.get("__od")):
-                out[_hashable(self.build(k, row_np, aux_np))] = self.build(v, row_np, aux_np)
+                out[_hashable(self.build(k, row_np, aux_np, built))] = self.build(v, row_np, aux_np, built)
             return out
         raise _WireError(na.FA_ERR_UNSUPPORTED, f"unknown manifest node {list(node)}")
 
 
 def _hashable(k):
     return tuple(_hashable(x) for x in k) if isinstance(k, list) else k
-
-
-def _payload_nodes(node, out):
-    if isinstance(node, list):
-        for x in node:
-            _payload_nodes(x, out)
-    elif isinstance(node, dict):
-        if "__nd" in node or "__sc" in node or "__b" in node:
-            out.append(node)
-        else:
-            for key in ("__t", "__d", "__od"):
-                if key in node:
-                    _payload_nodes(node[key], out)
 
 
 _GAPS: dict = {}  # row layout -> int64 indices of its alignment gaps
@@ -538,11 +547,11 @@ def _gap_index(layout: tuple) -> np.ndarray:
     idx = _GAPS.get(layout)
     if idx is None:
         parts, end = [], 0
-        for _k, shape, off in layout[:-1]:
+        for _k, shape, off in layout_slots(layout):
             if off > end:
                 parts.append(np.arange(end, off, dtype=np.int64))
-            end = off + _numel(shape)
-        parts.append(np.arange(end, layout[-1], dtype=np.int64))
+            end = off + math.prod(shape)
+        parts.append(np.arange(end, layout_stride(layout), dtype=np.int64))
         idx = np.concatenate(parts)
         if len(_GAPS) >= 64:
             _GAPS.clear()
@@ -551,43 +560,7 @@ def _gap_index(layout: tuple) -> np.ndarray:
 
 
 def _pinned_row(stride: int) -> torch.Tensor:
-    if torch.cuda.is_available():
-        return torch.empty(stride, dtype=torch.float32, pin_memory=True)
-    return torch.empty(stride, dtype=torch.float32)
-
-
-class _Template:
-    """Everything decode_fast derives from a scanner manifest alone: the parsed tree (read-only
-    from here on), the row plan, the aux-buffer layout and the payload ranges.  Uploads of one
-    model with the same weight produce the same manifest text (pickle lays the same dict out
-    the same way), so a round of N uploads plans once instead of N times."""
-
-    __slots__ = ("tree", "row_plan", "row_nodes", "aux_size", "planned", "offs", "lens", "rel", "in_row")
-
-    def __init__(self, L, p, n, tree):
-        dec = _Decoder(L, p, n)
-        self.planned = dec.plan_row(tree)
-        dec.assign(tree)
-        self.tree, self.row_plan, self.row_nodes, self.aux_size = tree, dec.row_plan, dec.row_nodes, dec.aux_size
-        offs, lens, rel, in_row = [], [], [], []
-        for node in _payload_nodes_list(tree):
-            if "__nd" in node:
-                o, ln = node["__nd"][3], node["__nd"][4]
-                row = "_aux" not in node
-                r = 4 * dec.row_plan[id(node)] if row else node["_aux"]
-            elif "__sc" in node:
-                o, ln, row, r = node["__sc"][1], node["__sc"][2], False, node["_aux"]
-            else:
-                (o, ln), row, r = node["__b"], False, node["_aux"]
-            if ln:
-                offs.append(o)
-                lens.append(ln)
-                rel.append(r)
-                in_row.append(row)
-        self.offs = np.array(offs, np.int64)
-        self.lens = np.array(lens, np.int64)
-        self.rel = np.array(rel, np.int64)
-        self.in_row = np.array(in_row, bool)
+    return torch.empty(stride, dtype=torch.float32, pin_memory=torch.cuda.is_available())
 
 
 _TEMPLATES: collections.OrderedDict = collections.OrderedDict()  # manifest text -> _Template
@@ -595,13 +568,13 @@ _TEMPLATES_MAX = 8
 _TEMPLATES_LOCK = threading.Lock()
 
 
-def _template(L, p, n, manifest: bytes) -> _Template:
+def _template(manifest: bytes) -> _Template:
     with _TEMPLATES_LOCK:
         t = _TEMPLATES.get(manifest)
         if t is not None:
             _TEMPLATES.move_to_end(manifest)
             return t
-    t = _Template(L, p, n, json.loads(manifest.decode("utf-8")))
+    t = _Template(json.loads(manifest.decode("utf-8")))
     with _TEMPLATES_LOCK:
         _TEMPLATES[manifest] = t
         while len(_TEMPLATES) > _TEMPLATES_MAX:
@@ -625,45 +598,37 @@ def decode_fast(s: str, stage_to_device: bool = False):
             continue
         _check(L, rc, "pickle scan")
         break
-    tmpl = _template(L, p, n, buf.raw[: need.value])
-    tree, planned = tmpl.tree, tmpl.planned
-    dec = _Decoder(L, p, n)
-    dec.row_plan, dec.row_nodes, dec.aux_size = tmpl.row_plan, tmpl.row_nodes, tmpl.aux_size
-    aux_np = np.empty(max(dec.aux_size, 1), dtype=np.uint8)
+    tmpl = _template(buf.raw[: need.value])
+    layout = tmpl.layout
+    aux_np = np.empty(max(tmpl.aux_size, 1), dtype=np.uint8)
     row, row_np = None, None
-    if planned is not None:
-        stride = planned[1][-1]
-        row = _pinned_row(stride)
+    if layout is not None:
+        row = _pinned_row(layout_stride(layout))
         row_np = row.numpy().view(_RowArray)
         row_np._fa_tensor = row
         # zero the alignment gaps (reduced but never returned: keep them finite and deterministic)
-        row_np[_gap_index(planned[1])] = 0
+        row_np[_gap_index(layout)] = 0
     if len(tmpl.offs):
         row_base = row_np.ctypes.data if row_np is not None else 0
         dsts = tmpl.rel + np.where(tmpl.in_row, row_base, aux_np.ctypes.data)
         rc = L.fa_b64_decode_ranges(p, n, len(tmpl.offs), tmpl.offs.ctypes.data, tmpl.lens.ctypes.data,
                                     dsts.ctypes.data, _threads(int(tmpl.lens.sum())))
         _check(L, rc, "payload decode")
-    obj = dec.build(tree, row_np, aux_np)
-    if planned is not None:
+    built = {}
+    obj = tmpl.build(tmpl.tree, row_np, aux_np, built)
+    if layout is not None:
         params = obj.get("params") if isinstance(obj, dict) else None
         if isinstance(params, dict):
             # the decoder's own views, laid out as planned (a key repeated in the pickled dict
             # would leave an earlier planned slot unreferenced: refuse rather than register it)
-            for (k, _shape, _off), node in zip(planned[1][:-1], dec.row_nodes):
-                if params.get(k) is not dec.row_built.get(id(node)):
+            for (k, _shape, _off), node in zip(layout_slots(layout), tmpl.row_nodes):
+                if params.get(k) is not built.get(id(node)):
                     raise _WireError(na.FA_ERR_DATA, f"decoded array {k!r} is not in its planned slot")
             staged = None
             if stage_to_device and torch.cuda.is_available() and row.is_pinned():
-                staged = _stage_for(planned[1]).stage(row)
-            _register(params, row_np, planned[1], staged)
+                staged = _stage_for(layout).stage(row)
+            _register(params, row_np, layout, staged)
     return obj
-
-
-def _payload_nodes_list(tree):
-    out = []
-    _payload_nodes(tree, out)
-    return out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@ print("scan ms", (time.perf_counter()-t)/10*1e3, need.value)
 tree = json.loads(buf.raw[:need.value].decode())
 t=time.perf_counter()
 for _ in range(10):
-    dec = wire._Decoder(L, ptr, n); planned = dec.plan_row(tree); dec.assign(tree)
+    tmpl = wire._Template(tree)  # the row plan, the aux layout and the payload ranges
 print("plan+assign ms", (time.perf_counter()-t)/10*1e3)
 out = np.empty(p+100000, np.float32)
 raw = wire.b64decode(s)

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 16
+ABI_VERSION = 17
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -29,6 +29,7 @@ MODE_H16_NUMPY, MODE_H16_TORCH, MODE_H16_NP16, MODE_H16_W32, MODE_H16_W64 = 0, 1
 OP_MEAN, OP_AVGM, OP_ADAGRAD, OP_YOGI, OP_ADAM, OP_DYN = 0, 1, 2, 3, 4, 5
 SRC_F64, SRC_I64, SRC_F32 = 0, 1, 2  # fa_gather_rows_f64 source kinds
 PREC_F32, PREC_F64 = 0, 1
+ACC_F32, ACC_F32_W64, ACC_F64, ACC_I64 = 0, 1, 2, 3  # fa_fold accumulator kinds (FA_ACC_*)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
 #: every symbol include/flearn_amd.h declares (checked by tests/test_cabi.py)
@@ -62,6 +63,8 @@ EXPORTS = (
     "fa_set_reduce_grid",
     "fa_reduce_windows",
     "fa_last_launch",
+    "fa_fold",
+    "fa_fold_finish",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -231,6 +234,8 @@ def load(require_gpu: bool = False):
                 "fa_set_reduce_grid": ([I32], ctypes.c_int),
                 "fa_reduce_windows": ([I32, I64], ctypes.c_int),
                 "fa_last_launch": ([ctypes.POINTER(LaunchRecord)], ctypes.c_int),
+                "fa_fold": ([I32, P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
+                "fa_fold_finish": ([I32, I32, P, D, I64, ctypes.POINTER(Epilogue), P, P, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _native as na
-from .bucketplan import SMALL_BYTES, TORCH_DTYPE, BucketPlan, Shard, _as_list, make_plan, rank_width
+from .bucketplan import SMALL_BYTES, TORCH_DTYPE, BucketPlan, Shard, _as_list, make_plan, rank_width, select_keys
 from .dist import DoubleBuffer, gather_columns
 from .packer import AsyncPack, NativeRows, Packer, piece_columns
 from .rowtable import RowTable
@@ -630,6 +630,32 @@ class DynState:
             return gbuf
         return gbuf.to(torch.float32)
 
+    def finish_step(self, agg: "Aggregator", sh, acc, acc_kind: int, nm: Numerics, want64: bool, n_clients: int):
+        """`step` for a streamed round (streaming.RoundAccumulator.finish): the sum over the round's
+        n_clients uploads is already in `acc`; fa_fold_finish divides and runs the same epilogue."""
+        from .streaming import fold_finish
+
+        hs, theta = self.state[sh.index]
+        th = theta.cur
+        f64 = th.dtype == torch.float64
+        self._dirty = True
+        if self._covered:
+            out32 = None if want64 else agg.packer.device_bucket(("out32", KIND_F32, sh.index), (sh.width,),
+                                                                   torch.float32, sh.device)
+            th_o = theta.other
+            epi = _epilogue(na.OP_DYN, None, th, h=hs, alpha=self.alpha, n_dyn=n_clients, v_out=th_o)
+            fold_finish(acc_kind, nm.mode, acc, nm.denom, sh.width, out32=out32, out64=th_o if want64 else None, epi=epi)
+            theta.flip()
+            return th_o if want64 else out32
+        gbuf = agg.packer.device_bucket(("dyn_g", KIND_F32, sh.index), (sh.width,), th.dtype, sh.device)
+        fold_finish(acc_kind, nm.mode, acc, nm.denom, sh.width, out32=None if f64 else gbuf, out64=gbuf if f64 else None)
+        for a, b in self._runs(sh):
+            gs = gbuf[a:b]
+            apply_dyn(gs, hs[a:b], th[a:b], n_clients, self.alpha, out64=gs if f64 else None, out32=None if f64 else gs)
+        if want64 or not f64:
+            return gbuf
+        return gbuf.to(torch.float32)
+
     def _runs(self, sh):
         """Maximal column runs [a, b) of device keys within the shard, shard-relative."""
         segs = sorted((s.offset, s.offset + s.numel) for s in self._plan.f32.segments if s.key in set(self.dev_keys))
@@ -749,10 +775,14 @@ class Aggregator:
     small_parts = 1
 
     def __init__(self, device=None, output: str = "reference", workers: int = 8, devices=None, group=None,
-                 reorder: bool = False):
+                 reorder: bool = False, chunk_clients: int | None = None):
         na.lib()  # fail loudly right away if the HIP path is unavailable
         if output not in OUTPUTS:
             raise ValueError(f"output must be one of {OUTPUTS}")
+        # chunk_clients = K: ensemble() runs the round through begin_round() in chunks of K clients
+        # (device memory O(K * stride): a round larger than HBM); None: one stack, one launch
+        self.chunk_clients = chunk_clients
+        self._chunk_packers = None  # the two staging / stack sets of streamed rounds (streaming.py)
         if group is not None and devices is not None and len(devices) > 1:
             raise ValueError("group (one GPU per process) and devices (several GPUs in this process) exclude each other")
         if devices is None:
@@ -813,7 +843,27 @@ class Aggregator:
         reduce_stack_f16(stack, w, nm.mode, nm.denom, **{name: out})
         return out
 
+    def begin_round(self, key_lst=None, server_opt=None, chunk_clients: int = 16):
+        """One round aggregated as it arrives (streaming.RoundAccumulator): `add(upload)` per
+        {"agg_weight", "params"} dict, folded in chunks of chunk_clients clients, then `finish()`,
+        which returns what `ensemble` returns for the same uploads, bit for bit."""
+        from .streaming import RoundAccumulator
+
+        return RoundAccumulator(self, key_lst, server_opt, chunk_clients)
+
+    def _ensemble_chunked(self, agg_weight_lst, w_local_lst, key_lst, server_opt):
+        if len(w_local_lst) == 0 or len(agg_weight_lst) == 0 or len(agg_weight_lst) != len(w_local_lst):
+            make_plan(agg_weight_lst, w_local_lst, key_lst)  # raises what the one-launch path raises
+        # the whole list is here: the reference's key intersection (strategy.py:119-121) as ever
+        # (and its length: no chunk stack taller than the round)
+        acc = self.begin_round(select_keys(w_local_lst, key_lst), server_opt, min(self.chunk_clients, len(w_local_lst)))
+        for a, w in zip(agg_weight_lst, w_local_lst):
+            acc.add({"agg_weight": a, "params": w})
+        return acc.finish()
+
     def ensemble(self, agg_weight_lst, w_local_lst, key_lst=None, server_opt: ServerOptimizer | None = None):
+        if self.chunk_clients is not None:
+            return self._ensemble_chunked(agg_weight_lst, w_local_lst, key_lst, server_opt)
         plan = make_plan(agg_weight_lst, w_local_lst, key_lst)
         self.last_plan = plan
         self._refuse_half(plan, server_opt)

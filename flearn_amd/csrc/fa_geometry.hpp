@@ -14,7 +14,7 @@
 
 namespace fa {
 
-enum Family { kFamRows, kFamNarrow, kFamRowmajor, kFamSplitn, kFamBalanced, kFamRowsH16 };
+enum Family { kFamRows, kFamNarrow, kFamRowmajor, kFamSplitn, kFamBalanced, kFamRowsH16, kFamFoldRows, kFamFoldElem };
 
 // One launch: the kernel family, the template arguments its dispatch varies, and the grid.
 struct Plan {
@@ -253,6 +253,35 @@ inline Plan plan_f16_window(int vmax, int64_t ncols, int cus) {
 inline int64_t balanced_grid(int64_t chunks, int64_t slots) {
   const int64_t grid = chunks < slots ? chunks : slots;
   return grid > 0 ? grid : 1;
+}
+
+// One chunk of a streamed round (fa_fold): acc_kind FA_ACC_*, the window's columns, on `cus` CUs;
+// forced: fa_set_reduce_grid (0 = the geometry chooses).
+//   * fp32 client rows (FA_ACC_F32 / _F32_W64): fold_kernel_rows on the one-piece sizing rules of
+//     the plain mean — 4 waves, ~0.75 blocks per CU, the narrowest piece (V KiB per wave) that
+//     covers the block's share, D = 64/(V*W) rows in flight (V*W*D = 64 KiB per block).  A window
+//     just past one round of full pieces takes a few more blocks, up to rows_grid_max (13/16 of the
+//     CUs), instead of a nearly empty second round; wider windows are swept piece after piece
+//     (column-major, 64-KiB pieces, D = 1) on the natural grid.  The chunk's client count does not
+//     enter: the kernel's ramp and drain are correct for any K against D.
+//   * 8-byte kinds (FA_ACC_F64 / _I64): fold_kernel_elem, grid-stride, one column per lane, at
+//     most 4 blocks per CU.
+constexpr int kFoldW = 4;
+inline Plan plan_fold_window(int acc_kind, int64_t ncols, int cus, int forced = 0) {
+  if (acc_kind == FA_ACC_F64 || acc_kind == FA_ACC_I64) {
+    const int64_t blocks = ceil_div(ncols, 256), cap = forced > 0 ? forced : (int64_t)cus * 4;
+    return Plan{kFamFoldElem, 1, 4, 1, 0, 0, false, blocks < 1 ? 1 : (blocks < cap ? blocks : cap)};
+  }
+  const int64_t chunks = row_chunks(ncols);
+  int64_t grid = forced > 0 ? forced : natural_grid(cus);
+  if (forced <= 0 && chunks > grid * kPieceChunks && chunks <= rows_grid_max(cus) * kPieceChunks)
+    grid = ceil_div(chunks, kPieceChunks);
+  if (grid > chunks) grid = chunks;
+  if (grid < 1) grid = 1;
+  const int64_t share = ceil_div(chunks, grid);  // chunks per block
+  int v = 1;  // the narrowest piece that covers the share; past one round: full 64-KiB pieces
+  while (v < kPieceChunks / kFoldW && share > v * kFoldW) v *= 2;
+  return Plan{kFamFoldRows, v, kFoldW, kPieceChunks / (v * kFoldW), 0, 0, false, grid};
 }
 
 }  // namespace fa

@@ -39,7 +39,7 @@ int fail(int code, const char* what) {
   return code;
 }
 
-// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* call launched.  A launch
+// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* call launched.  A launch
 // stores a pointer and two integers; the name is built once per instantiation (a static of its
 // launch site, as resident_blocks_per_cu keeps its occupancy).
 struct LaunchRecord {
@@ -482,6 +482,54 @@ int reduce_8byte(const typename P::x_t* stack, int64_t row_stride, int32_t n_cli
   return launch_balanced(a, static_cast<hipStream_t>(stream));
 }
 
+// fa_fold: one chunk of a streamed round.  plan_fold_window chooses the piece width and the grid;
+// FIRST (no acc_in) is a block-uniform branch of the kernel, so only the policy and V are
+// template arguments.
+template <class P>
+int launch_fold_rows(const Plan& p, const float* stack, int64_t stride, int n, const void* w, const void* acc_in,
+                     void* acc_out, int64_t col0, int64_t ncols, hipStream_t s) {
+  typedef typename P::acc_t A;
+  const typename P::w_t* wt = static_cast<const typename P::w_t*>(w);
+  const A* ai = static_cast<const A*>(acc_in);
+  A* ao = static_cast<A*>(acc_out);
+#define FA_FOLD_ROWS(V)                                                                                          \
+  case V:                                                                                                        \
+    FA_LAUNCH_AS(HInst, fold_kernel_rows, (P, V, kPieceChunks / (V * kFoldW), kFoldW, kNT), p.grid, 64 * kFoldW, \
+                 s, stack, stride, n, wt, ai, ao, col0, ncols);                                                  \
+    return launch_check()
+  if (p.W == kFoldW && p.D == kPieceChunks / (p.V * kFoldW)) {
+    switch (p.V) {
+      FA_FOLD_ROWS(1);
+      FA_FOLD_ROWS(2);
+      FA_FOLD_ROWS(4);
+      FA_FOLD_ROWS(8);
+      FA_FOLD_ROWS(16);
+    }
+  }
+#undef FA_FOLD_ROWS
+  return no_kernel("fold_kernel_rows");
+}
+
+template <class P>
+int launch_fold_elem(const Plan& p, const void* stack, int64_t stride, int n, const void* w, const void* acc_in,
+                     void* acc_out, int64_t col0, int64_t ncols, hipStream_t s) {
+  typedef typename P::acc_t A;
+  FA_LAUNCH_AS(HInst, fold_kernel_elem, (P), p.grid, kThreads, s, static_cast<const typename P::x_t*>(stack), stride,
+               n, static_cast<const typename P::w_t*>(w), static_cast<const A*>(acc_in), static_cast<A*>(acc_out), col0,
+               ncols);
+  return launch_check();
+}
+
+// fa_fold_finish: one quad per lane over the accumulator (A), result precision T, op OP
+template <class AT, typename T, auto... X>
+struct FInst {};  // the naming tag: fold_finish_kernel<A,T,OP>
+template <typename A, int OP, typename T>
+int launch_fold_finish(const A* acc, int64_t n, const Epi<T>& e, hipStream_t s) {
+  const int64_t blocks = (n + kThreads * 4 - 1) / (kThreads * 4);
+  FA_LAUNCH_AS(FInst, fold_finish_kernel, (A, T, OP), blocks, kThreads, s, acc, n, e);
+  return launch_check();
+}
+
 // fa_gather_rows*: the shared argument checks (`bad`: the entry's own complaint, checked after
 // them), then one launch(grid, i0) per tile of up to 65535 clients (the grid's y limit)
 template <class F>
@@ -744,6 +792,75 @@ int fa_last_launch(fa_launch_record* out) {
   out->launches = g_last_launch.launches;
   out->reserved = 0;
   return FA_OK;
+}
+
+int fa_fold(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients, const void* weights,
+            const void* acc_in, void* acc_out, int64_t col_begin, int64_t n_cols, void* stream) {
+  g_last_launch = LaunchRecord{};
+  if (acc_kind < FA_ACC_F32 || acc_kind > FA_ACC_I64) return fail(FA_ERR_ARG, "unknown accumulator kind");
+  if (int rc = check_window(stack, row_stride, n_clients, weights, col_begin, n_cols, acc_out != nullptr)) return rc;
+  const bool wide = acc_kind == FA_ACC_F64 || acc_kind == FA_ACC_I64;
+  const bool fp64sum = acc_kind != FA_ACC_F32;
+  if (wide ? !aligned_window(static_cast<const double*>(stack), row_stride, col_begin)
+           : !aligned_window(static_cast<const float*>(stack), row_stride, col_begin))
+    return fail(FA_ERR_ALIGN, "row window not 16-B aligned");
+  if (!aligned_to(acc_in, 16) || !aligned_to(acc_out, 16)) return fail(FA_ERR_ALIGN, "accumulator must be 16-B aligned");
+  if (acc_in && acc_in != acc_out && overlaps(acc_in, acc_out, (size_t)n_cols * (fp64sum ? 8 : 4)))
+    return fail(FA_ERR_ARG, "acc_out must be acc_in or an array not overlapping it");
+  if (n_cols == 0) return FA_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const Plan p = plan_fold_window(acc_kind, n_cols, device_cus(), g_reduce_grid.load(std::memory_order_relaxed));
+  switch (acc_kind) {
+    case FA_ACC_F32:
+      return launch_fold_rows<AccF32>(p, static_cast<const float*>(stack), row_stride, n_clients, weights, acc_in,
+                                      acc_out, col_begin, n_cols, s);
+    case FA_ACC_F32_W64:
+      return launch_fold_rows<AccF32W64>(p, static_cast<const float*>(stack), row_stride, n_clients, weights, acc_in,
+                                         acc_out, col_begin, n_cols, s);
+    case FA_ACC_F64:
+      return launch_fold_elem<AccF64>(p, stack, row_stride, n_clients, weights, acc_in, acc_out, col_begin, n_cols, s);
+    default:
+      return launch_fold_elem<AccI64>(p, stack, row_stride, n_clients, weights, acc_in, acc_out, col_begin, n_cols, s);
+  }
+}
+
+int fa_fold_finish(int32_t acc_kind, int32_t mode, const void* acc, double denom, int64_t n_cols,
+                   const fa_epilogue* epi, float* out32, double* out64, void* stream) {
+  g_last_launch = LaunchRecord{};
+  if (acc_kind < FA_ACC_F32 || acc_kind > FA_ACC_I64) return fail(FA_ERR_ARG, "unknown accumulator kind");
+  if (n_cols < 0 || !acc) return fail(FA_ERR_ARG, "bad accumulator");
+  if (!out32 && !out64) return fail(FA_ERR_ARG, "no output");
+  const int op = epi ? epi->op : FA_OP_MEAN;
+  const bool fp32rows = acc_kind == FA_ACC_F32 || acc_kind == FA_ACC_F32_W64;
+  if (!fp32rows && op != FA_OP_MEAN) return fail(FA_ERR_ARG, "an epilogue needs an fp32 accumulator kind");
+  if (acc_kind == FA_ACC_F32 && mode != FA_MODE_W32_DIV64 && mode != FA_MODE_W32_DIV32)
+    return fail(FA_ERR_ARG, "FA_ACC_F32 needs mode FA_MODE_W32_DIV64 or FA_MODE_W32_DIV32");
+  if (acc_kind == FA_ACC_F32_W64 && mode != FA_MODE_W64) return fail(FA_ERR_ARG, "FA_ACC_F32_W64 needs mode FA_MODE_W64");
+  // there is no reduce to take N from
+  if (op == FA_OP_DYN && !(epi->n_clients > 0)) return fail(FA_ERR_ARG, "FedDyn finish needs n_clients > 0");
+  if (!aligned_to(acc, 16)) return fail(FA_ERR_ALIGN, "accumulator must be 16-B aligned");
+  const bool f32res = acc_kind == FA_ACC_F32 && mode == FA_MODE_W32_DIV32;
+  if (int rc = check_columns(out32, out64, epi ? epi->prev : nullptr, epi ? epi->v : nullptr,
+                             f32res ? sizeof(float) : sizeof(double), epi ? epi->h : nullptr))
+    return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  auto go = [&](auto a, auto t) {
+    typedef decltype(a) A;
+    typedef decltype(t) T;
+    Epi<T> e;
+    if (int rc = make_epi(epi, denom, 0, out32, out64, &e, n_cols)) return rc;
+    if (n_cols == 0) return (int)FA_OK;
+    if constexpr (std::is_same<A, int64_t>::value) {
+      return launch_fold_finish<A, FA_OP_MEAN>(static_cast<const A*>(acc), n_cols, e, s);
+    } else {
+      return with_op(op, [&](auto OP) { return launch_fold_finish<A, OP()>(static_cast<const A*>(acc), n_cols, e, s); });
+    }
+  };
+  switch (acc_kind) {
+    case FA_ACC_F32: return f32res ? go(float{}, float{}) : go(float{}, double{});
+    case FA_ACC_I64: return go(int64_t{}, double{});
+    default: return go(double{}, double{});  // FA_ACC_F32_W64 / FA_ACC_F64 (plain mean only, checked above)
+  }
 }
 
 int fa_copy(void* dst, const void* src, int64_t nbytes, void* stream) {

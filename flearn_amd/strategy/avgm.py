@@ -17,8 +17,8 @@ class AVGM(AVG):
     """Mean momentum (Hsu et al., arXiv:1909.06335)."""
 
     def __init__(self, encrypt=None, output="reference", device=None, server_side=False, beta=0.9, devices=None,
-                 group=None):
-        super().__init__(encrypt, output, device, devices, group)
+                 group=None, chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
         self.server_side = server_side
         self.beta = beta
         self._updater = None
@@ -32,6 +32,9 @@ class AVGM(AVG):
 
             self._server_opt = ServerOptimizer("avgm", beta=self.beta)
         return self._server_opt
+
+    def _round_spec(self, first_params):
+        return None, (self.server_opt if self.server_side else None)
 
     def server(self, ensemble_params_lst, round_):
         if not self.server_side:

@@ -13,6 +13,9 @@ class BN(AVG):
             w_shared["params"].pop(k)
         return w_shared
 
+    def _round_spec(self, first_params):
+        return [k for k in first_params if "bn" not in k], None
+
     def server(self, ensemble_params_lst, round_):
         _, w_local_lst = self.server_pre_processing(ensemble_params_lst)
         try:

@@ -28,6 +28,10 @@ class Distill(AVG):
         ensemble_params["glob_logits"] = self.aggregate_logits(logits_lst, self.__dict__.get("device"))
         return ensemble_params
 
+    def _round_done(self, w_glob, uploads):
+        logits_lst = self.extract_lst(uploads, "logits")
+        return {"w_glob": w_glob, "glob_logits": self.aggregate_logits(logits_lst, self.__dict__.get("device"))}
+
     def client_receive(self, trainer, server_p_bytes):
         """distill.py:38-40: load w_glob, keep the global logits on the trainer's device."""
         server_p = super().client_receive(trainer, server_p_bytes)

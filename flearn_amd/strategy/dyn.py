@@ -23,8 +23,9 @@ from .avg import AVG
 class Dyn(AVG):
     """Federated learning based on dynamic regularization (Acar et al., ICLR 2021)."""
 
-    def __init__(self, h, encrypt=None, output="reference", device=None, devices=None, group=None):
-        super().__init__(encrypt, output, device, devices, group)
+    def __init__(self, h, encrypt=None, output="reference", device=None, devices=None, group=None,
+                 chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
         from ..aggregator import DynState
 
         self._dyn = DynState(h, alpha=0.01)  # alpha: dyn.py:15
@@ -60,6 +61,19 @@ class Dyn(AVG):
     def server_post_processing(self, ensemble_params_lst, ensemble_params):
         """dyn.py:38-41 — the FedDyn step is fused into the reduce; nothing left to do here."""
         return ensemble_params
+
+    def _round_spec(self, first_params):
+        h = self._dyn.h_host
+        if h is None:
+            raise AttributeError("'NoneType' object has no attribute 'keys'")  # dyn.py:20
+        for k in h:  # dyn.py:21 indexes w_glob[k]: the round's keys are the first upload's
+            if first_params is None or k not in first_params:
+                raise KeyError(k)
+        return None, self._dyn
+
+    def _round_done(self, w_glob, uploads):
+        self._theta = w_glob  # dyn.py:34
+        return {"w_glob": w_glob}
 
     def server(self, ensemble_params_lst, round_):
         """dyn.py:43-45: AVG.server, then the FedDyn step (one fused launch)."""

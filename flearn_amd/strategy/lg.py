@@ -8,8 +8,8 @@ from .utils import convert_to_tensor
 
 class LG(AVG):
     def __init__(self, shared_key_layers=None, encrypt=None, output="reference", device=None, devices=None,
-                 group=None):
-        super().__init__(encrypt, output, device, devices, group)
+                 group=None, chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
         self.shared_key_layers = shared_key_layers
 
     def client(self, trainer, agg_weight=1.0):
@@ -18,6 +18,9 @@ class LG(AVG):
             for k in [k for k in w_shared["params"].keys() if k not in self.shared_key_layers]:
                 w_shared["params"].pop(k)
         return w_shared
+
+    def _round_spec(self, first_params):
+        return self.shared_key_layers, None
 
     def server(self, ensemble_params_lst, round_):
         return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, key_lst=self.shared_key_layers)}

@@ -8,8 +8,8 @@ from .utils import convert_to_tensor
 
 class LG_R(AVG):
     def __init__(self, shared_key_layers=None, encrypt=None, output="reference", device=None, devices=None,
-                 group=None):
-        super().__init__(encrypt, output, device, devices, group)
+                 group=None, chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
         self.shared_key_layers = shared_key_layers
 
     def client(self, trainer, agg_weight=1.0):

@@ -19,8 +19,8 @@ class OPT(AVG):
     """Adaptive federated optimization (Reddi et al., arXiv:2003.00295)."""
 
     def __init__(self, encrypt=None, output="reference", device=None, server_side=False, method="adagrad",
-                 devices=None, group=None):
-        super().__init__(encrypt, output, device, devices, group)
+                 devices=None, group=None, chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
         self.server_side = server_side
         self.method = method.lower()
         if self.method not in _METHODS:
@@ -36,6 +36,9 @@ class OPT(AVG):
 
             self._server_opt = ServerOptimizer(self.method, eta=self.eta, tau=self.tau, beta2=self.beta2)
         return self._server_opt
+
+    def _round_spec(self, first_params):
+        return None, (self.server_opt if self.server_side else None)
 
     def server(self, ensemble_params_lst, round_):
         if not self.server_side:

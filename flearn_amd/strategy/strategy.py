@@ -17,6 +17,10 @@ Extra keyword arguments (all optional, defaults keep the reference's behaviour):
               (flearn_amd.dist; True = the default process group)
     reorder : (attribute, default False) allow the split-N kernel for narrow models with many
               clients — deterministic and within 1e-6 normwise of the reference, not bit-exact
+    chunk_clients : K — server() aggregates the round in chunks of K clients (Aggregator.begin_round:
+              device memory O(K x model), a round larger than HBM), bit-identical to the default
+              (None: one client stack, one launch).  `begin_round(round_)` returns a handle for
+              aggregating uploads as they arrive.
 """
 from __future__ import annotations
 
@@ -52,12 +56,14 @@ class BaseEncrypt:
 
 
 class Strategy(ABC):
-    def __init__(self, encrypt=None, output: str = "reference", device=None, devices=None, group=None):
+    def __init__(self, encrypt=None, output: str = "reference", device=None, devices=None, group=None,
+                 chunk_clients=None):
         self.encrypt = BaseEncrypt() if encrypt is None else encrypt
         self.output = output
         self.device = device
         self.devices = devices
         self.group = group
+        self.chunk_clients = chunk_clients
         self._engine = None
 
     # -- engine -----------------------------------------------------------------------------
@@ -70,7 +76,7 @@ class Strategy(ABC):
             d = self.__dict__
             self._engine = Aggregator(device=d.get("device"), output=d.get("output", "reference"),
                                       devices=d.get("devices"), group=d.get("group"),
-                                      reorder=bool(d.get("reorder", False)))
+                                      reorder=bool(d.get("reorder", False)), chunk_clients=d.get("chunk_clients"))
         return self._engine
 
     # -- reference surface ------------------------------------------------------------------
@@ -122,6 +128,24 @@ class Strategy(ABC):
         except _CLIENT_DATA_ERRORS as e:  # the reference's convention (avg.py:28-31)
             self.server_exception(e)
 
+    # -- a round aggregated as it arrives ------------------------------------------------------
+    def _round_spec(self, first_params):
+        """(key_lst, server_opt) server() hands the engine for a round whose first upload carries
+        `first_params`: the hook begin_round() shares with server()."""
+        return None, None
+
+    def _round_done(self, w_glob, uploads):
+        """What server() returns for the aggregated w_glob; uploads: the round's upload dicts
+        without their "params" (released chunk by chunk)."""
+        return {"w_glob": w_glob}
+
+    def begin_round(self, round_):
+        """A handle for one round aggregated as uploads arrive: `add(upload)` takes an upload dict
+        (or, in HTTP mode, the encoded string: it goes through receive_processing), `finish()` returns
+        what `server(all uploads, round_)` returns, bit for bit.  Chunks of `chunk_clients` (16 when
+        unset) clients are packed and folded while later uploads are still on their way."""
+        return StrategyRound(self, round_)
+
     @abstractmethod
     def client(self, trainer, agg_weight=1.0):
         return NotImplemented
@@ -133,6 +157,47 @@ class Strategy(ABC):
     @abstractmethod
     def client_receive(self, trainer, w_glob_b):
         return NotImplemented
+
+
+class StrategyRound:
+    """Strategy.begin_round's handle (the engine's RoundAccumulator behind the strategy's hooks).
+    Client-data errors take server()'s route, server_exception -> SystemExit; device errors propagate.
+    server_post_processing sees the uploads without their "params" ({"agg_weight": a, ...} per
+    upload): the params are released as soon as their chunk is folded."""
+
+    def __init__(self, strategy, round_):
+        self.strategy, self.round_ = strategy, round_
+        self._acc = None
+        self._seen = []
+
+    def _guard(self, fn, *args):
+        try:
+            return fn(*args)
+        except _DEVICE_ERRORS:
+            raise
+        except _CLIENT_DATA_ERRORS as e:
+            self.strategy.server_exception(e)
+
+    def _begin(self, first_params):
+        s = self.strategy
+        # (an empty round has no first upload: finish() then raises what server([]) raises)
+        key_lst, server_opt = (None, None) if first_params is None else s._round_spec(first_params)
+        k = s.__dict__.get("chunk_clients")
+        self._acc = s.engine.begin_round(key_lst, server_opt, 16 if k is None else k)
+
+    def add(self, upload):
+        if isinstance(upload, (str, bytes, bytearray)):
+            upload = self.strategy.receive_processing(upload)
+        if self._acc is None:
+            self._begin(upload["params"])
+        self._guard(self._acc.add, upload)
+        self._seen.append({k: v for k, v in upload.items() if k != "params"})
+
+    def finish(self):
+        if self._acc is None:
+            self._begin(None)
+        w_glob = self._guard(self._acc.finish)
+        return self.strategy.server_post_processing(self._seen, self.strategy._round_done(w_glob, self._seen))
 
 
 class ParentStrategy(Strategy):
@@ -150,3 +215,6 @@ class ParentStrategy(Strategy):
 
     def client_receive(self, trainer, w_glob_b):
         return self.strategy.client_receive(trainer, w_glob_b)
+
+    def begin_round(self, round_):
+        return self.strategy.begin_round(round_)

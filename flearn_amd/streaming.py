@@ -1,0 +1,303 @@
+"""A round aggregated in chunks of clients: `RoundAccumulator` (Aggregator.begin_round).
+
+The reference's sum is a running one — w = a0*x0; w += a_n*x_n in list order
+(flearn/common/strategy/strategy.py:123-126) — so the engine does not need the whole [N][stride]
+client stack at once.  Uploads are buffered until `chunk_clients` are present, packed with the
+existing Packer on a chunk-sized plan of the same layout, and folded into a typed accumulator
+(fa_fold); `finish()` divides by np.sum over the WHOLE weight list and applies the optional server
+update (fa_fold_finish, strategy.py:127-129, avgm.py / opt.py / dyn.py).  Results are bit-identical
+to `Aggregator.ensemble` on the same list; device memory is O(chunk_clients * stride) whatever the
+client count, and uploads are aggregated as they arrive.
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+
+import numpy as np
+import torch
+
+from . import _native as na
+from .bucketplan import TORCH_DTYPE, BucketPlan, Group, _as_array_meta, make_plan
+from .packer import Packer
+from .rowtable import RowTable
+from .semantics import KIND_F32, KIND_F64, KIND_I64, _is_weight, resolve
+
+_F16, _F64 = np.dtype(np.float16), np.dtype(np.float64)
+_ACC_TORCH = {na.ACC_F32: torch.float32, na.ACC_F32_W64: torch.float64, na.ACC_F64: torch.float64,
+              na.ACC_I64: torch.int64}
+
+
+def acc_kind_of(kind: str, mode: int) -> int:
+    """FA_ACC_* of a bucket kind under its numerics' mode (the sum type np.result_type gives)."""
+    if kind == KIND_F32:
+        return na.ACC_F32_W64 if mode == na.MODE_W64 else na.ACC_F32
+    return {KIND_F64: na.ACC_F64, KIND_I64: na.ACC_I64}[kind]
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def fold_stack(acc_kind: int, stack: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+               col_begin: int = 0, n_cols: int | None = None, n_clients: int | None = None) -> None:
+    """acc_out = acc_in + sum_i weights[i] * stack[i] over the chunk's rows in list order (fa_fold),
+    queued on torch's current stream.  acc_in None: the chunk opens the round (its first product
+    initialises the sum).  acc_out may be acc_in."""
+    n = stack.shape[0] if n_clients is None else n_clients
+    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
+    if stack.dim() != 2 or stack.stride(1) != 1 or not stack.is_cuda:
+        raise ValueError("stack must be a 2-D device tensor with contiguous rows")
+    adt = _ACC_TORCH[acc_kind]
+    for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
+        if t is not None and (t.dtype != adt or not t.is_cuda or t.numel() < ncols or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {adt} device tensor of at least {ncols} elements")
+    if weights.numel() < n or not 1 <= n <= stack.shape[0]:
+        raise ValueError("fewer weights or rows than clients")
+    rc = na.lib().fa_fold(acc_kind, stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), _ptr(acc_in),
+                          acc_out.data_ptr(), col_begin, ncols, na.stream_handle(stack.device))
+    na.check(rc, "fa_fold")
+
+
+def fold_finish(acc_kind: int, mode: int, acc: torch.Tensor, denom: float, n_cols: int, *, out32=None, out64=None,
+                epi: na.Epilogue | None = None) -> None:
+    """The divide by `denom` and the optional server update over a finished accumulator
+    (fa_fold_finish), queued on torch's current stream."""
+    rc = na.lib().fa_fold_finish(acc_kind, mode, acc.data_ptr(), float(denom), n_cols,
+                                 ctypes.byref(epi) if epi is not None else None, _ptr(out32), _ptr(out64),
+                                 na.stream_handle(acc.device))
+    na.check(rc, "fa_fold_finish")
+
+
+class RoundAccumulator:
+    """One round aggregated as it arrives: `add(upload)` per {"agg_weight", "params"} dict, then
+    `finish()`, which returns exactly what `Aggregator.ensemble` returns for the same uploads.
+
+    The layout and key set come from the first upload (or key_lst): every later upload must carry
+    those keys with the same shapes and dtypes; extra keys are ignored.  The sum type of each bucket
+    is np.result_type(weight, dtype) as semantics.resolve decides it, fixed by the first upload; the
+    divide mode, the denominator and the output dtype come from resolve() on the whole weight list at
+    finish().  `reorder` does not apply: a streamed round is always bit-exact."""
+
+    def __init__(self, agg, key_lst=None, server_opt=None, chunk_clients: int = 16):
+        if agg._dist:
+            raise ValueError("a streamed round is not sharded over a process group (group=): use ensemble()")
+        if len(agg.devices) > 1:
+            raise ValueError("a streamed round runs on one device: devices=[...] with several devices is not supported")
+        if not isinstance(chunk_clients, (int, np.integer)) or isinstance(chunk_clients, bool) or chunk_clients < 1:
+            raise ValueError("chunk_clients must be an integer >= 1")
+        self.agg = agg
+        self.chunk_clients = int(chunk_clients)
+        self.server_opt = server_opt
+        self._key_lst = None if key_lst is None else list(key_lst)
+        self._keys = None  # fixed by the first upload
+        self._meta = None  # key -> (dtype, shape)
+        self._input_kind = None
+        self._acc_dtype = {}  # tensor dtype -> the sum dtype np.result_type gives under the weights
+        self._pending = []  # uploads of the chunk being collected
+        self._weights = []  # every weight so far (the divide needs the whole list)
+        self._acc = {}  # bucket kind -> the accumulator holding the sum so far
+        self._layout = None  # the first chunk's plan: groups, segments, strides
+        self._chunks = 0
+        self._finished = False
+        self.max_stack_rows = 0  # the most client rows any packed chunk had
+
+    # -- uploads ----------------------------------------------------------------------------
+    def add(self, upload) -> None:
+        if self._finished:
+            raise RuntimeError("add() after finish(): begin a new round")
+        w, params = upload["agg_weight"], upload["params"]
+        if not _is_weight(w):
+            raise TypeError(f"agg_weight must be a real scalar, got {type(w).__name__}")
+        if self._keys is None:
+            self._first(w, params)
+        else:
+            self._check(w, params)
+        self._weights.append(w)
+        self._pending.append((w, params))
+        if len(self._pending) == self.chunk_clients:
+            self._fold_pending()
+
+    def _first(self, w, params) -> None:
+        keys = list(params.keys()) if self._key_lst is None else self._key_lst
+        meta, kinds, acc = {}, set(), {}
+        for k in keys:
+            if k not in params:
+                raise KeyError(k)
+            dt, shape, ik = _as_array_meta(params[k], f"client 0 key {k!r}")
+            if dt == _F16:  # refused before anything is queued, as Aggregator._refuse_half does
+                raise TypeError("float16 uploads: a streamed round aggregates fp32 / float64 / int64 buckets only "
+                                "(use ensemble() without chunk_clients for a model.half() client)")
+            meta[k] = (dt, tuple(shape))
+            kinds.add(ik)
+            if dt not in acc:
+                acc[dt] = resolve([w], dt).acc_dtype
+        if len(kinds) > 1:
+            raise TypeError("mixing numpy arrays and torch tensors in one aggregation is not supported")
+        self._keys, self._meta, self._acc_dtype = keys, meta, acc
+        self._input_kind = kinds.pop() if kinds else "numpy"
+
+    def _check(self, w, params) -> None:
+        n = len(self._weights)
+        for k in self._keys:
+            if k not in params:
+                raise KeyError(k)
+            dt, shape, ik = _as_array_meta(params[k], f"client {n} key {k!r}")
+            dt0, shape0 = self._meta[k]
+            if dt != dt0 or tuple(shape) != shape0:
+                raise ValueError(f"client {n} key {k!r}: {dt}{list(shape)} does not match client 0's {dt0}{list(shape0)}")
+            if ik != self._input_kind:
+                raise TypeError("mixing numpy arrays and torch tensors in one aggregation is not supported")
+        for dt, a0 in self._acc_dtype.items():
+            a = np.result_type(w, dt)
+            if a != a0:
+                raise TypeError(
+                    "agg_weight types promote differently (" + ", ".join(sorted(map(str, {a, a0}))) + "); "
+                    "the reference would mix precisions per client — use one weight type")
+
+    # -- folding ----------------------------------------------------------------------------
+    def _packer(self) -> Packer:
+        """Two staging and stack sets alternate: chunk c + 1 is packed into the other set's pinned
+        staging while chunk c's copies and fold run; a set's staging is rewritten only after the
+        copy queued from it last has completed (Packer._staging waits for that event), and its
+        device stack only by copies queued, on the same stream, behind the fold that read it."""
+        agg = self.agg
+        if getattr(agg, "_chunk_packers", None) is None:
+            agg._chunk_packers = (agg.packer, Packer(agg.devices, agg.packer.workers))
+        return agg._chunk_packers[self._chunks % 2]
+
+    def chunk_plan(self, ws, ps) -> BucketPlan:
+        """The chunk-sized plan of the round's layout (host only): the existing make_plan over the
+        chunk's uploads and weights — the same keys, segments, offsets and strides as a plan of the
+        whole list, the chunk's weights cast as numpy casts them."""
+        plan = make_plan(ws, ps, self._keys)
+        if self._layout is None:
+            self._layout = plan
+        elif any(k not in self._layout.groups or self._layout.groups[k].stride != g.stride
+                 for k, g in plan.groups.items()) or len(plan.groups) != len(self._layout.groups):
+            raise TypeError("agg_weight types promote differently between chunks; use one weight type")
+        return plan
+
+    def numerics(self, x_dtype):
+        """semantics.resolve on the WHOLE weight list so far: the divide mode, np.sum over the list as
+        the reference computes it, and the output dtype (why the divide is not fused into a fold)."""
+        return resolve(self._weights, x_dtype)
+
+    def _fold_pending(self) -> None:
+        ws = [w for w, _ in self._pending]
+        ps = [p for _, p in self._pending]
+        self._pending = []
+        plan = self.chunk_plan(ws, ps)
+        agg, packer = self.agg, self._packer()
+        dev = agg.device
+        if self._chunks == 0:
+            # both sets' chunk stacks at their full K rows from the first chunk on: what the round holds
+            # on the device does not depend on how many uploads follow (device_bytes)
+            for p in agg._chunk_packers:
+                for kind, g in plan.groups.items():
+                    p.device_bucket(("in", kind, 0), (self.chunk_clients, g.stride), TORCH_DTYPE[g.store_dtype], dev)
+        stacks = packer.pack(plan, ps)
+        self.max_stack_rows = max(self.max_stack_rows, len(ps))
+        with torch.cuda.device(dev):
+            for kind, parts in stacks.items():
+                g = plan.groups[kind]
+                ((sh, stack),) = parts
+                if isinstance(stack, RowTable):  # device uploads: the one-launch gather into the chunk stack
+                    buf = packer.device_bucket(("in", kind, sh.index), (len(ps), g.stride), TORCH_DTYPE[g.store_dtype],
+                                               sh.device)
+                    stack.gather_into(buf)
+                    stack = buf
+                ak = acc_kind_of(kind, g.numerics.mode)
+                acc = agg.packer.device_bucket(("acc", kind), (g.stride,), _ACC_TORCH[ak], dev)
+                fold_stack(ak, stack, agg._weights(g.numerics, dev), self._acc.get(kind), acc, n_clients=len(ps))
+                self._acc[kind] = acc
+                if packer.last_row_tables.get(kind) == "slab":  # the caller's memory, read in place
+                    packer.hold([stack], dev)
+        self._chunks += 1
+
+    # -- the end of the round -----------------------------------------------------------------
+    def _final_plan(self) -> BucketPlan:
+        """The round's plan: the layout of the chunks, the numerics of the WHOLE weight list."""
+        lay = self._layout
+        groups = {}
+        for kind, g in lay.groups.items():
+            nm = self.numerics(g.segments[0].src_dtype)
+            if nm.kind != kind or acc_kind_of(kind, nm.mode) != acc_kind_of(kind, g.numerics.mode):
+                raise TypeError("agg_weight types promote differently over the round; use one weight type")
+            groups[kind] = Group(kind, nm, g.segments, g.stride)
+        return dataclasses.replace(lay, groups=groups, n_clients=len(self._weights), memo={})
+
+    def finish(self):
+        if self._finished:
+            raise RuntimeError("finish() was already called: begin a new round")
+        self._finished = True
+        if not self._weights:
+            make_plan([], [], self._key_lst)  # raises what ensemble([], []) raises
+        if self._pending:
+            self._fold_pending()
+        agg, so = self.agg, self.server_opt
+        plan = self._final_plan()
+        agg.last_plan = plan
+        agg._post_denom = None
+        n = len(self._weights)
+        fused = False
+        if so is not None and KIND_F32 in plan.groups:
+            fused = so.prepare(plan, agg.packer.shards(plan, KIND_F32))
+        results, first_means = {}, {}
+        for kind, g in plan.groups.items():
+            (sh,) = agg.packer.shards(plan, kind)
+            nm = g.numerics
+            ak = acc_kind_of(kind, nm.mode)
+            acc = self._acc[kind]
+            with torch.cuda.device(sh.device):
+                if kind == KIND_F32:
+                    out = self._finish_f32(plan, sh, acc, ak, nm, n, fused, first_means)
+                else:
+                    out = agg.packer.device_bucket(("out64", kind, sh.index), (sh.width,), torch.float64, sh.device)
+                    fold_finish(ak, nm.mode, acc, nm.denom, sh.width, out64=out)
+            results[kind] = [(sh, out)]
+        if so is not None and first_means:
+            so.adopt(plan, agg.packer.shards(plan, KIND_F32), first_means)
+        return agg._finish(plan, results)
+
+    def _finish_f32(self, plan, sh, acc, ak, nm, n, fused, first_means):
+        """Aggregator._reduce_f32 with the sum already made: the same outputs, the same state protocol
+        (the double-buffered state advances only once the launch call has returned)."""
+        from .aggregator import DynState, _epilogue
+
+        agg, so = self.agg, self.server_opt
+        bucket = agg.packer.device_bucket
+        want64 = agg.output == "reference" and nm.out_dtype == _F64
+        out64 = bucket(("out64", KIND_F32, sh.index), (sh.width,), torch.float64, sh.device) if want64 else None
+        if isinstance(so, DynState):
+            return so.finish_step(agg, sh, acc, ak, nm, want64, n)
+        if so is not None and fused:
+            prev, v, prev_o, v_o = so.step_buffers(sh)
+            epi = _epilogue(so.op, prev, v, so.beta, so.eta, so.tau, so.beta2, v_out=v_o)
+            fold_finish(ak, nm.mode, acc, nm.denom, sh.width, out32=prev_o, out64=out64, epi=epi)
+            so.advance(sh)
+            return out64 if want64 else prev_o
+        out32 = None
+        if not want64 or so is not None:
+            out32 = bucket(("out32", KIND_F32, sh.index), (sh.width,), torch.float32, sh.device)
+        fold_finish(ak, nm.mode, acc, nm.denom, sh.width, out32=out32, out64=out64)
+        if so is not None:
+            first_means[sh.index] = out32
+        return out64 if want64 else out32
+
+    # -- memory -------------------------------------------------------------------------------
+    @property
+    def device_bytes(self) -> int:
+        """Bytes of chunk stacks, accumulators and outputs this round holds on the device: it does
+        not depend on how many uploads were added."""
+        agg = self.agg
+        total = 0
+        packers = getattr(agg, "_chunk_packers", None) or (agg.packer,)
+        seen = set()
+        for p in packers:
+            for (tag, _dev), t in p._dev.items():
+                name = tag[0] if isinstance(tag, tuple) else tag
+                if name in ("in", "acc", "out32", "out64", "dyn_g") and id(t) not in seen:
+                    seen.add(id(t))
+                    total += t.numel() * t.element_size()
+        return total

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 16
+#define FA_ABI_VERSION 17
 
 /* return codes */
 #define FA_OK 0
@@ -270,7 +270,7 @@ int fa_set_reduce_grid(int32_t grid);
 int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
- * _i64 / _f16 call launched.  For tests and profilers that must know which kernel instantiation a
+ * _i64 / _f16 / fa_fold / fa_fold_finish call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -288,6 +288,46 @@ typedef struct fa_launch_record {
   int32_t reserved; /* 0 */
 } fa_launch_record;
 int fa_last_launch(fa_launch_record* out);
+
+/* ---- a round aggregated in chunks of clients (streamed rounds) -----------
+ * The reference's sum is a running one: w = a0*x0; w += a_n*x_n in list order
+ * (flearn/common/strategy/strategy.py:123-126).  fa_fold adds one chunk of K client rows to a typed
+ * accumulator that the caller carries from chunk to chunk; after the last chunk it holds the bits
+ * the single launch's sum holds.  fa_fold_finish then divides by np.sum(a) over the WHOLE weight
+ * list (strategy.py:127-129) and applies the optional server update.  A round's device memory is
+ * then O(K * row_stride), whatever the client count, and uploads can be folded as they arrive.
+ * ABI 17.                                                                                        */
+#define FA_ACC_F32 0     /* fp32 rows x float weights (FA_MODE_W32_DIV64 / _DIV32): float sums     */
+#define FA_ACC_F32_W64 1 /* fp32 rows x double weights (FA_MODE_W64): double sums                  */
+#define FA_ACC_F64 2     /* double rows x double weights: double sums                              */
+#define FA_ACC_I64 3     /* int64 rows x int64 weights: int64 sums, wrapping as numpy's do         */
+
+/* acc_out[c] = acc_in[c] + sum_i weights[i] * stack[i][col_begin + c] over the chunk's n_clients
+ * rows in list order (acc = acc + fl(w*x), no fused multiply-add; int64 wraps) — strategy.py:
+ * 124-126 for clients after the first.  acc_in == NULL: the chunk opens the round and its first
+ * product initialises the sum, strategy.py:123 (so a column that is -0.0 in every client stays
+ * -0.0).  stack / weights have the element types of the table above; the accumulator has the sum
+ * type, is indexed from 0 at col_begin and is 16-byte aligned (FA_ERR_ALIGN otherwise, as for a
+ * misaligned row window; nothing is launched).  acc_out may equal acc_in (each element is read
+ * before it is written) or be another array (double-buffered); a partial overlap, n_clients < 1
+ * or an unknown kind is FA_ERR_ARG.  Nothing outside acc_out[0, n_cols) is written; n_cols == 0 is
+ * a no-op.  fa_set_reduce_grid applies.                                                          */
+int fa_fold(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients,
+            const void* weights, const void* acc_in, void* acc_out,
+            int64_t col_begin, int64_t n_cols, void* stream);
+
+/* The end of a streamed round: q = acc / denom as np.divide(w, np.sum(a)) gives it
+ * (strategy.py:127-129) — FA_ACC_F32: mode FA_MODE_W32_DIV64 q = fl64(acc) / denom, mode
+ * FA_MODE_W32_DIV32 q = acc / fl32(denom); FA_ACC_F32_W64 (mode FA_MODE_W64) and FA_ACC_F64:
+ * q = acc / denom; FA_ACC_I64: q = (double)acc / denom; mode is ignored for the 8-byte kinds —
+ * then the optional server update with g = q: FA_OP_AVGM (avgm.py:19-36), FA_OP_ADAGRAD / _YOGI /
+ * _ADAM (opt.py:23-65), FA_OP_DYN (dyn.py:17-36), the device functions fa_reduce_f32's fused
+ * epilogue runs, with the same stores to out32 / out64 and the state.  An epilogue is accepted
+ * only for the two fp32 kinds; FA_OP_DYN needs epi->n_clients > 0 here (there is no reduce to take
+ * N from) — FA_ERR_ARG otherwise, as for an unknown kind or a v_out overlapping v.  acc is 16-byte
+ * aligned, the per-column arrays as for fa_reduce_f32 (FA_ERR_ALIGN).  n_cols == 0 is a no-op.  */
+int fa_fold_finish(int32_t acc_kind, int32_t mode, const void* acc, double denom, int64_t n_cols,
+                   const fa_epilogue* epi, float* out32, double* out64, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

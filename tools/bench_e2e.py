@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--ab", default=None,
                     help="alternate round by round between Packer settings, e.g. "
                          "'native_async=0;native_async=1,async_lookahead=2': per-setting medians")
+    ap.add_argument("--chunk-clients", type=int, default=None,
+                    help="alternate round by round between the one-launch path and chunk_clients=K (a streamed "
+                         "round, DESIGN.md section 11): total time per server call, same process, results compared")
     a = ap.parse_args()
     name, n = CONFIGS[a.config]
     layout = layouts.get(name)
@@ -66,6 +69,8 @@ def main():
         eng.packer.async_lookahead = a.lookahead
     if a.pack_threads is not None:
         eng.packer.async_threads = a.pack_threads
+    if a.chunk_clients is not None:
+        return chunked_ab(a, s, uploads, n, p)
     # phase timers around the engine's own steps
     t = {"plan_pack_h2d": [], "reduce": [], "d2h_unpack": [], "total": []}
     orig_pack, orig_finish = eng.packer.pack, eng._finish
@@ -122,6 +127,31 @@ def main():
         "note": "uploads are host numpy views (flearn loopback); first round (pinned-buffer allocation) excluded",
     }
     print(json.dumps(res))
+
+
+def chunked_ab(a, s, uploads, n, p):
+    """Round r runs the one-launch path (r even) or chunk_clients=K (r odd) on the same uploads;
+    medians of the whole server call over the rounds after each path's first; results bit-equal."""
+    eng = s.engine
+    per, ref = {"one_launch": [], "chunked": []}, None
+    for r in range((a.rounds + 1) * 2):
+        eng.chunk_clients = a.chunk_clients if r % 2 else None
+        t0 = time.perf_counter()
+        w_glob = s.server(uploads, r)["w_glob"]
+        per["chunked" if r % 2 else "one_launch"].append(time.perf_counter() - t0)
+        if ref is None:
+            ref = w_glob
+        elif r < 2:
+            assert all(np.asarray(w_glob[k]).tobytes() == np.asarray(ref[k]).tobytes() for k in ref), "results differ"
+    eng.chunk_clients = None
+    med = {k: float(np.median(v[1:])) for k, v in per.items()}
+    nbytes = n * p * 4 + p * (8 if a.output == "reference" else 4)
+    print(json.dumps({
+        "config": a.config, "clients": n, "params": p, "output": a.output, "chunk_clients": a.chunk_clients,
+        "rounds_per_path": a.rounds, "median_s": {k: round(v, 5) for k, v in med.items()},
+        "e2e_GiB_s_algorithmic": {k: round(nbytes / 2**30 / v, 2) for k, v in med.items()},
+        "chunked_vs_one_launch": round(med["chunked"] / med["one_launch"], 4),
+        "total_ms_all": {k: [round(x * 1e3, 1) for x in v] for k, v in per.items()}}))
 
 
 def ab(a, s, uploads, t, layout):

@@ -38,6 +38,7 @@ import warnings
 import torch
 import torch.distributed as dist
 
+from .ops import reduce_stack
 from .push import (MAX_PUSH_RANKS, PARK_CAP, DeviceBuffer, HipIpc, PushGather, _all_ok, _group_alive,  # noqa: F401
                    _IPC, _LARGEST, _map_peers, _PARKED, _PUSH_ORDER, _RecvPool, _resolve_group, _TRIMMED, _unmap_all,
                    peer_stream, push_order, shutdown_push, side_stream, size_class)
@@ -123,7 +124,7 @@ class ShardedReducer:
     """Runs one aggregation step on this rank's shard and reassembles the full bucket.
 
     reduce_fn(col_begin, n_cols, out_slice) reduces local columns [col_begin, +n_cols) into
-    out_slice — on a GPU it is the HIP kernel (aggregator.reduce_stack); the CPU tests inject
+    out_slice — on a GPU it is the HIP kernel (ops.reduce_stack); the CPU tests inject
     the oracle to check the sharding and gather logic with gloo.
     """
 
@@ -228,9 +229,7 @@ def hip_reduce_fn(stack, weights, mode, denom, reorder=False, state: PingPong | 
     Epilogue state: a PingPong (double-buffered: the step reads its current pair, writes the
     model into out_slice — the PingPong's `out` — and v_t into the other v), or prev / v
     local-column tensors updated in place.  reorder: allow the split-N kernel
-    (aggregator.reduce_stack)."""
-    from .aggregator import reduce_stack
-
+    (ops.reduce_stack)."""
     prev, v = epilogue.pop("prev", None), epilogue.pop("v", None)
 
     def fn(col_begin, n_cols, out_slice):

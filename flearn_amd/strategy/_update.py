@@ -18,10 +18,11 @@ import numpy as np
 import torch
 
 from .. import _native as na
-from .. import aggregator  # its _epilogue / apply_update are called through the module (tests patch them there)
+from .. import ops  # its _epilogue / apply_update are called through the module (tests patch them there)
 from ..bucketplan import FMT, padded_span
 from ..dist import DoubleBuffer
 from ..packer import AsyncPack, NativeRows, pack_threads
+from ..serverstate import _as_host
 
 _F32 = np.dtype(np.float32)
 _DEV_GLOB = (np.dtype(np.float64), _F32)  # w_glob dtypes the device path takes
@@ -331,7 +332,7 @@ class DeviceUpdater:
             done = set(batch)
             keys = [k for k in keys if k not in done]
         for k in keys:
-            lv, g = aggregator._as_host(w_local[k]), aggregator._as_host(w_glob[k])
+            lv, g = _as_host(w_local[k]), _as_host(w_glob[k])
             delta = g - lv
             v = vh.get(k)
             if v is None:
@@ -397,7 +398,7 @@ class DeviceUpdater:
             out = torch.empty(total, dtype=tdt, device=dev)
             params = dict(self.params, **override)
             kw = {"out64": out} if tdt == torch.float64 else {"out32": out}
-            aggregator.apply_update(self.op, ld, gd, self.v.cur, **kw, **params)
+            ops.apply_update(self.op, ld, gd, self.v.cur, **kw, **params)
             oh.copy_(out, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()  # staging is reused by the next call
         # one fresh array for the new w_local, filled from the pinned result by the pool
@@ -500,8 +501,8 @@ class DeviceUpdater:
                         out = (d.dout if dma_out else res)[first:end].data_ptr()
                     else:  # the kernel reads the pinned staging and writes the pinned result over PCIe
                         src_l, src_g, out = lh[first:end], gh[first:end], res[first:end].data_ptr()
-                    epi = aggregator._epilogue(self.op, src_l, v_in[first:end], p["beta"], p["eta"], p["tau"],
-                                               p["beta2"], v_out=v_out[first:end])
+                    epi = ops._epilogue(self.op, src_l, v_in[first:end], p["beta"], p["eta"], p["tau"],
+                                        p["beta2"], v_out=v_out[first:end])
                     na.check(L.fa_opt_apply(prec, ctypes.byref(epi), src_l.data_ptr(), src_g.data_ptr(),
                                             end - first, None if prec == na.PREC_F64 else out,
                                             out if prec == na.PREC_F64 else None, sh), "fa_opt_apply")
@@ -600,8 +601,8 @@ class DeviceUpdater:
                     feed.wait(j)
                     first, end = c.first, c.end
                     dg[first:end].copy_(gh[first:end], non_blocking=True)
-                    epi = aggregator._epilogue(self.op, dl[first:end], v_in[first:end], p["beta"], p["eta"], p["tau"],
-                                               p["beta2"], v_out=v_out[first:end])
+                    epi = ops._epilogue(self.op, dl[first:end], v_in[first:end], p["beta"], p["eta"], p["tau"],
+                                        p["beta2"], v_out=v_out[first:end])
                     out = dout[first:end].data_ptr()
                     na.check(L.fa_opt_apply(prec, ctypes.byref(epi), dl[first:end].data_ptr(), dg[first:end].data_ptr(),
                                             end - first, None if prec == na.PREC_F64 else out,

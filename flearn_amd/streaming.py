@@ -11,62 +11,18 @@ client count, and uploads are aggregated as they arrive.
 """
 from __future__ import annotations
 
-import ctypes
 import dataclasses
 
 import numpy as np
 import torch
 
-from . import _native as na
 from .bucketplan import TORCH_DTYPE, BucketPlan, Group, _as_array_meta, make_plan
+from .ops import _ACC_TORCH, FoldedSum, acc_kind_of, fold_finish, fold_stack  # noqa: F401 (re-exported)
 from .packer import Packer
 from .rowtable import RowTable
-from .semantics import KIND_F32, KIND_F64, KIND_I64, _is_weight, resolve
+from .semantics import _is_weight, resolve
 
 _F16, _F64 = np.dtype(np.float16), np.dtype(np.float64)
-_ACC_TORCH = {na.ACC_F32: torch.float32, na.ACC_F32_W64: torch.float64, na.ACC_F64: torch.float64,
-              na.ACC_I64: torch.int64}
-
-
-def acc_kind_of(kind: str, mode: int) -> int:
-    """FA_ACC_* of a bucket kind under its numerics' mode (the sum type np.result_type gives)."""
-    if kind == KIND_F32:
-        return na.ACC_F32_W64 if mode == na.MODE_W64 else na.ACC_F32
-    return {KIND_F64: na.ACC_F64, KIND_I64: na.ACC_I64}[kind]
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def fold_stack(acc_kind: int, stack: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
-               col_begin: int = 0, n_cols: int | None = None, n_clients: int | None = None) -> None:
-    """acc_out = acc_in + sum_i weights[i] * stack[i] over the chunk's rows in list order (fa_fold),
-    queued on torch's current stream.  acc_in None: the chunk opens the round (its first product
-    initialises the sum).  acc_out may be acc_in."""
-    n = stack.shape[0] if n_clients is None else n_clients
-    ncols = stack.shape[1] - col_begin if n_cols is None else n_cols
-    if stack.dim() != 2 or stack.stride(1) != 1 or not stack.is_cuda:
-        raise ValueError("stack must be a 2-D device tensor with contiguous rows")
-    adt = _ACC_TORCH[acc_kind]
-    for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
-        if t is not None and (t.dtype != adt or not t.is_cuda or t.numel() < ncols or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {adt} device tensor of at least {ncols} elements")
-    if weights.numel() < n or not 1 <= n <= stack.shape[0]:
-        raise ValueError("fewer weights or rows than clients")
-    rc = na.lib().fa_fold(acc_kind, stack.data_ptr(), stack.stride(0), n, weights.data_ptr(), _ptr(acc_in),
-                          acc_out.data_ptr(), col_begin, ncols, na.stream_handle(stack.device))
-    na.check(rc, "fa_fold")
-
-
-def fold_finish(acc_kind: int, mode: int, acc: torch.Tensor, denom: float, n_cols: int, *, out32=None, out64=None,
-                epi: na.Epilogue | None = None) -> None:
-    """The divide by `denom` and the optional server update over a finished accumulator
-    (fa_fold_finish), queued on torch's current stream."""
-    rc = na.lib().fa_fold_finish(acc_kind, mode, acc.data_ptr(), float(denom), n_cols,
-                                 ctypes.byref(epi) if epi is not None else None, _ptr(out32), _ptr(out64),
-                                 na.stream_handle(acc.device))
-    na.check(rc, "fa_fold_finish")
 
 
 class RoundAccumulator:
@@ -235,55 +191,15 @@ class RoundAccumulator:
             make_plan([], [], self._key_lst)  # raises what ensemble([], []) raises
         if self._pending:
             self._fold_pending()
-        agg, so = self.agg, self.server_opt
+        agg = self.agg
         plan = self._final_plan()
         agg.last_plan = plan
-        agg._post_denom = None
-        n = len(self._weights)
-        fused = False
-        if so is not None and KIND_F32 in plan.groups:
-            fused = so.prepare(plan, agg.packer.shards(plan, KIND_F32))
-        results, first_means = {}, {}
+        sums = {}  # the server step Aggregator.ensemble runs, over the sums already made
         for kind, g in plan.groups.items():
             (sh,) = agg.packer.shards(plan, kind)
-            nm = g.numerics
-            ak = acc_kind_of(kind, nm.mode)
-            acc = self._acc[kind]
-            with torch.cuda.device(sh.device):
-                if kind == KIND_F32:
-                    out = self._finish_f32(plan, sh, acc, ak, nm, n, fused, first_means)
-                else:
-                    out = agg.packer.device_bucket(("out64", kind, sh.index), (sh.width,), torch.float64, sh.device)
-                    fold_finish(ak, nm.mode, acc, nm.denom, sh.width, out64=out)
-            results[kind] = [(sh, out)]
-        if so is not None and first_means:
-            so.adopt(plan, agg.packer.shards(plan, KIND_F32), first_means)
-        return agg._finish(plan, results)
-
-    def _finish_f32(self, plan, sh, acc, ak, nm, n, fused, first_means):
-        """Aggregator._reduce_f32 with the sum already made: the same outputs, the same state protocol
-        (the double-buffered state advances only once the launch call has returned)."""
-        from .aggregator import DynState, _epilogue
-
-        agg, so = self.agg, self.server_opt
-        bucket = agg.packer.device_bucket
-        want64 = agg.output == "reference" and nm.out_dtype == _F64
-        out64 = bucket(("out64", KIND_F32, sh.index), (sh.width,), torch.float64, sh.device) if want64 else None
-        if isinstance(so, DynState):
-            return so.finish_step(agg, sh, acc, ak, nm, want64, n)
-        if so is not None and fused:
-            prev, v, prev_o, v_o = so.step_buffers(sh)
-            epi = _epilogue(so.op, prev, v, so.beta, so.eta, so.tau, so.beta2, v_out=v_o)
-            fold_finish(ak, nm.mode, acc, nm.denom, sh.width, out32=prev_o, out64=out64, epi=epi)
-            so.advance(sh)
-            return out64 if want64 else prev_o
-        out32 = None
-        if not want64 or so is not None:
-            out32 = bucket(("out32", KIND_F32, sh.index), (sh.width,), torch.float32, sh.device)
-        fold_finish(ak, nm.mode, acc, nm.denom, sh.width, out32=out32, out64=out64)
-        if so is not None:
-            first_means[sh.index] = out32
-        return out64 if want64 else out32
+            ak = acc_kind_of(kind, g.numerics.mode)
+            sums[kind] = [(sh, FoldedSum(self._acc[kind], ak, len(self._weights), sh.width))]
+        return agg._finish(plan, agg._server_step(plan, sums, self.server_opt))
 
     # -- memory -------------------------------------------------------------------------------
     @property

@@ -153,13 +153,13 @@ def test_fused_round_refused_keeps_optimizer_state(cuda, monkeypatch):
     leaves the double-buffered state on the pair it had, so the rounds after it still match the
     reference: the step only fetches its buffers (ServerOptimizer.step_buffers) and the state
     advances to the pair it wrote (advance: DoubleBuffer.flip) after the launch call returned."""
-    from flearn_amd import aggregator
+    from flearn_amd import ops
 
     name = next(n for n in ROUND_CASES if Golden(n).meta["op"] == "avgm")
     g = Golden(name)
     s = AVGM(server_side=True)
     s.server_opt.init_global({k[6:]: v for k, v in g.arrays.items() if k.startswith("prev0:")})
-    real = aggregator.reduce_stack
+    real = ops.reduce_stack
     for r in range(g.meta["rounds"]):
         clients, weights = _round_inputs(g, r)
         if r == 1:  # one refused attempt of round 1 first
@@ -168,10 +168,10 @@ def test_fused_round_refused_keeps_optimizer_state(cuda, monkeypatch):
                     raise ValueError("refused launch")
                 return real(*a, **k)
 
-            monkeypatch.setattr(aggregator, "reduce_stack", refuse)
+            monkeypatch.setattr(ops, "reduce_stack", refuse)
             with pytest.raises(SystemExit):  # client/config data errors take server_exception
                 s.server(upload(clients, weights), r)
-            monkeypatch.setattr(aggregator, "reduce_stack", real)
+            monkeypatch.setattr(ops, "reduce_stack", real)
         got = s.server(upload(clients, weights), r)["w_glob"]
         assert_dict_bitwise(got, g.output(f"w{r}"), f"{name} w{r}")
         assert_dict_bitwise(s.server_opt.v_t(s.engine.last_plan), g.output(f"v{r}"), f"{name} v{r}")
@@ -1237,7 +1237,7 @@ def test_client_side_update_failure_mid_call_changes_nothing(op, transfer, cuda,
     queued) must leave v_t and w_local as they were — v_t is double-buffered and swapped only
     after every chunk ran, and the queued chunks are waited for before the error propagates — so
     retrying the round gives the reference's result."""
-    from flearn_amd import aggregator
+    from flearn_amd import ops
     from flearn_amd.strategy._update import DeviceUpdater
 
     monkeypatch.setattr(DeviceUpdater, "zero_copy", True)
@@ -1248,7 +1248,7 @@ def test_client_side_update_failure_mid_call_changes_nothing(op, transfer, cuda,
     prev = {k: rng.standard_normal(sh).astype(np.float32) for k, sh in shapes.items()}
     s = AVGM() if op == "avgm" else OPT()
     v = None
-    real = aggregator._epilogue
+    real = ops._epilogue
     for r in range(3):
         glob = {k: rng.standard_normal(sh) for k, sh in shapes.items()}
         if r == 1:
@@ -1260,12 +1260,12 @@ def test_client_side_update_failure_mid_call_changes_nothing(op, transfer, cuda,
                     raise ValueError("refused chunk")
                 return real(*a, **k)
 
-            monkeypatch.setattr(aggregator, "_epilogue", failing)
+            monkeypatch.setattr(ops, "_epilogue", failing)
             wl = dict(prev)
             with pytest.raises(ValueError, match="refused chunk"):
                 s.mean_momentum(wl, glob, 0.9) if op == "avgm" else s.adaptive_opt(wl, glob, op)
             assert calls["n"] == 3 and all(wl[k] is prev[k] for k in prev)
-            monkeypatch.setattr(aggregator, "_epilogue", real)
+            monkeypatch.setattr(ops, "_epilogue", real)
             if v is not None:
                 assert_dict_bitwise(s.v_t, v, f"{op} v after the failed call")
         if op == "avgm":

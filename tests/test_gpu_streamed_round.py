@@ -387,12 +387,12 @@ def test_later_uploads_off_the_layout_exit_through_the_strategy(k, cuda):
 def test_refused_fused_round_leaves_the_state(cuda, monkeypatch):
     """A streamed fused round whose finish launch is refused leaves v_t and the previous global model
     bit-equal to before it; the rounds after it still match the reference."""
-    from flearn_amd import streaming
+    from flearn_amd import ops
 
     g = Golden("avgm_pyfloat_rounds3")
     s = _fused("avgm", chunk_clients=2)
     s.server_opt.init_global(_prev0(g))
-    real = streaming.fold_finish
+    real = ops.fold_finish
     for r in range(g.meta["rounds"]):
         clients, weights = _round_inputs(g, r)
         if r == 1:
@@ -403,10 +403,10 @@ def test_refused_fused_round_leaves_the_state(cuda, monkeypatch):
                     raise ValueError("refused launch")
                 return real(*a, **k)
 
-            monkeypatch.setattr(streaming, "fold_finish", refuse)
+            monkeypatch.setattr(ops, "fold_finish", refuse)
             with pytest.raises(SystemExit):
                 s.server(upload(clients, weights), r)
-            monkeypatch.setattr(streaming, "fold_finish", real)
+            monkeypatch.setattr(ops, "fold_finish", real)
             after = s.server_opt.state_dict()
             assert_dict_bitwise(after["v_t"], before["v_t"], "v_t after a refused round")
             assert_dict_bitwise(after["w_glob"], before["w_glob"], "previous global model after a refused round")

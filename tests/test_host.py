@@ -561,34 +561,53 @@ def test_server_optimizer_state_advances_only_when_told():
     _assert_same(opt.v_t(), {k: np.zeros_like(x) for k, x in v0.items()})
 
 
-def test_dyn_state_theta_advances_only_after_the_launch_returned(monkeypatch):
-    """DynState.step with the launch replaced: a refused one leaves theta_host() on the loaded
-    values, one that returned shows what it wrote into v_out; h is handed over in place."""
-    from flearn_amd import aggregator
+@pytest.mark.parametrize("shape", ["stack", "folded"])
+def test_dyn_state_theta_advances_only_after_the_launch_returned(shape, monkeypatch):
+    """DynState.step over a sum whose launch is the test's: a refused one leaves theta_host() on the
+    loaded values, one that returned shows what it wrote into v_out; h is handed over in place.
+    "stack": a fake shaped like ops.StackSum whose mean is that launch (the one-launch round).
+    "folded": the real ops.FoldedSum.mean (a streamed round), under which ops.fold_finish is a CPU
+    stand-in that decodes the epilogue it is handed back into the state's tensors."""
+    from types import SimpleNamespace
+
+    from flearn_amd import ops
     from flearn_amd.aggregator import DynState
 
     model, plan, shards = _two_cpu_shards()
     dyn = DynState({k: x.copy() for k, x in model.items()})
     assert dyn.prepare(plan, shards)
-    seen = []
+    nm = plan.f32.numerics
+    seen, refuse = [], [True]
 
-    def launch(stack, w, mode, denom, *, out32, out64, op, v, v_out, h, alpha, refuse=False):
+    def launch(nm_, denom, *, out32, out64, op, v, v_out, h, alpha):
+        assert nm_ is nm and denom == nm.denom and alpha == dyn.alpha
         assert op == na.OP_DYN and out64 is v_out and out32 is None and not _shares_bytes(v, v_out)
         assert h.dtype == torch.float32 and v.dtype == torch.float64 and h.numel() == v.numel() == v_out.numel()
         seen.append(h)
-        if refuse:
+        if refuse[0]:
             raise ValueError("refused launch")
         v_out.copy_(v + 1)
 
+    if shape == "stack":
+        totals = [SimpleNamespace(stack=None, weights=None, reorder=False, n_clients=2, mean=launch) for _ in shards]
+    else:
+        state = {t.data_ptr(): t for hs, theta in dyn.state.values() for t in (hs, theta.cur, theta.other)}
+        totals = [ops.FoldedSum(torch.zeros(sh.width), na.ACC_F32, 2, sh.width) for sh in shards]
+
+        def finish(acc_kind, mode, acc, denom, n_cols, *, out32=None, out64=None, epi=None):
+            assert (acc_kind, mode, n_cols) == (na.ACC_F32, nm.mode, acc.numel())
+            assert epi.n_clients == 2.0 and epi.prev is None
+            launch(nm, denom, out32=out32, out64=out64, op=epi.op, v=state[epi.v], v_out=state[epi.v_out],
+                   h=state[epi.h], alpha=epi.alpha)
+
+        monkeypatch.setattr(ops, "fold_finish", finish)
     theta0 = {k: x.astype(np.float64) for k, x in model.items()}
-    nm = plan.f32.numerics
-    monkeypatch.setattr(aggregator, "reduce_stack", lambda *a, **k: launch(*a, refuse=True, **k))
-    for sh in shards:
+    for sh, total in zip(shards, totals):
         with pytest.raises(ValueError, match="refused launch"):
-            dyn.step(None, sh, None, None, nm, True)
+            dyn.step(None, sh, total, nm, True)
     _assert_same(dyn.theta_host(), theta0)
-    monkeypatch.setattr(aggregator, "reduce_stack", launch)
-    outs = [dyn.step(None, sh, None, None, nm, True) for sh in shards]
+    refuse[0] = False
+    outs = [dyn.step(None, sh, total, nm, True) for sh, total in zip(shards, totals)]
     assert [o.numel() for o in outs] == [sh.width for sh in shards]
     _assert_same(dyn.theta_host(), {k: x + 1 for k, x in theta0.items()})
     assert all(seen[i] is seen[i + 2] for i in range(2))  # h: the same array every round

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 17
+ABI_VERSION = 18
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -30,6 +30,7 @@ OP_MEAN, OP_AVGM, OP_ADAGRAD, OP_YOGI, OP_ADAM, OP_DYN = 0, 1, 2, 3, 4, 5
 SRC_F64, SRC_I64, SRC_F32 = 0, 1, 2  # fa_gather_rows_f64 source kinds
 PREC_F32, PREC_F64 = 0, 1
 ACC_F32, ACC_F32_W64, ACC_F64, ACC_I64 = 0, 1, 2, 3  # fa_fold accumulator kinds (FA_ACC_*)
+TRIM_MAX_CLIENTS = 128  # fa_trim_sum's deepest client stack (FA_TRIM_MAX_CLIENTS)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
 #: every symbol include/flearn_amd.h declares (checked by tests/test_cabi.py)
@@ -65,6 +66,7 @@ EXPORTS = (
     "fa_last_launch",
     "fa_fold",
     "fa_fold_finish",
+    "fa_trim_sum",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -236,6 +238,7 @@ def load(require_gpu: bool = False):
                 "fa_last_launch": ([ctypes.POINTER(LaunchRecord)], ctypes.c_int),
                 "fa_fold": ([I32, P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_fold_finish": ([I32, I32, P, D, I64, ctypes.POINTER(Epilogue), P, P, P], ctypes.c_int),
+                "fa_trim_sum": ([I32, P, I64, I32, I32, P, I64, I64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

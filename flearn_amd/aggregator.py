@@ -5,7 +5,8 @@ flearn/common/strategy/strategy.py:102-130: plan the buckets (bucketplan.py), co
 HBM, run ONE fused reduce launch per bucket kind on torch's current stream, and hand back a
 fresh dict with the reference's value types.  `begin_round` aggregates the same round in chunks of
 clients (streaming.py); both end in the same server step (`Aggregator._server_step`), fed by
-either kind of weighted sum (ops.StackSum, ops.FoldedSum).
+either kind of weighted sum (ops.StackSum, ops.FoldedSum).  `ensemble_trimmed` is the robust round:
+coordinate-wise trimmed sums (ops.trim_sum_stack) into the same server step.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
 (`ServerOptimizer`, `DynState`) serverstate.py, the small-host-round fast path smallround.py; every
@@ -13,17 +14,20 @@ name this module defined before it was split is re-exported here as the same obj
 """
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 import torch
 
 from . import _native as na
 from . import smallround
-from .bucketplan import BucketPlan, Shard, make_plan, rank_width, select_keys
+from .bucketplan import TORCH_DTYPE, BucketPlan, Group, Shard, make_plan, rank_width, select_keys
 from .dist import gather_columns
 from .ops import (FoldedSum, StackSum, _byte_range, _check_arrays, _check_cuda, _check_stack, _check_v_out,  # noqa: F401
                   _check_weights, _check_window, _epilogue, _ptr, _reduce_stack8, apply_dyn, apply_update, fill_uniform,
                   last_launch, mean_tables, reduce_stack, reduce_stack_f16, reduce_stack_f64, reduce_stack_i64,
                   set_reduce_grid)
+from .ops import _ACC_TORCH, acc_kind_of, trim_sum_stack
 from .packer import Packer
 from .rowtable import RowTable
 from .semantics import KIND_F16, KIND_F32, Numerics
@@ -157,6 +161,63 @@ class Aggregator:
         if self._dist and KIND_F32 in results:
             results[KIND_F32] = self._gather_columns(plan, results[KIND_F32])
         return self._finish(plan, results)
+
+    # -- robust rounds: coordinate-wise trimmed mean and median ----------------------------------
+    def ensemble_trimmed(self, w_local_lst, trim: int, key_lst=None, server_opt: ServerOptimizer | None = None):
+        """The coordinate-wise trimmed mean of the uploads (Yin et al., ICML 2018): per element, the
+        N clients' values in IEEE totalOrder, the `trim` smallest and the `trim` largest dropped, the
+        rest summed in ascending order in the bucket's sum type and divided by N - 2 * trim (the
+        median is trim = (N - 1) // 2).  There are no weights: a client cannot buy influence with
+        its own agg_weight, and the result does not depend on the order of the uploads.  The plan is
+        make_plan's for Python-int weights (key intersection, layouts and errors as in `ensemble`),
+        the uploads are packed as ever (host, device, slab), fa_trim_sum makes each bucket's sums,
+        and the server step — the divide, a fused AVGM / OPT update, the three output modes — is
+        the one a streamed round ends in.
+
+        Refused before anything is queued: float16 buckets and FedDyn state (TypeError: its h
+        update needs the plain sum over all N); several devices, group= and chunk_clients
+        (ValueError: every client must be present for a column's order statistics); more than
+        128 clients and a trim outside 0 <= 2 * trim < N (ValueError)."""
+        if self.chunk_clients is not None:
+            raise ValueError("a robust round needs every client at once: chunk_clients is not supported")
+        if self._dist:
+            raise ValueError("a robust round is not sharded over a process group (group=)")
+        if len(self.devices) > 1:
+            raise ValueError("a robust round runs on one device: devices=[...] with several devices is not supported")
+        if isinstance(server_opt, DynState):
+            raise TypeError("FedDyn's h update needs the plain sum over all clients: no robust round with Dyn state")
+        n = len(w_local_lst)
+        if n > na.TRIM_MAX_CLIENTS:
+            raise ValueError(f"a robust round takes at most {na.TRIM_MAX_CLIENTS} clients, got {n}")
+        plan = make_plan([1] * n, w_local_lst, key_lst)
+        if KIND_F16 in plan.groups:
+            raise TypeError("float16 uploads: a robust round aggregates fp32 / float64 / int64 buckets only")
+        if isinstance(trim, bool) or not isinstance(trim, (int, np.integer)) or trim < 0 or 2 * trim >= n:
+            raise ValueError(f"trim must be an integer with 0 <= 2 * trim < {n} clients, got {trim!r}")
+        trim = int(trim)
+        # the divide is by the kept count (the plan is make_plan's cached one: a copy carries it)
+        groups = {kind: Group(kind, dataclasses.replace(g.numerics, denom=float(n - 2 * trim)), g.segments, g.stride)
+                  for kind, g in plan.groups.items()}
+        plan = dataclasses.replace(plan, groups=groups)
+        self.last_plan = plan
+        stacks = self.packer.pack(plan, w_local_lst)
+        sums = {}
+        for kind, parts in stacks.items():
+            g = plan.groups[kind]
+            ((sh, stack),) = parts
+            with torch.cuda.device(sh.device):
+                if isinstance(stack, RowTable):  # device uploads: the one-launch gather into the stack
+                    buf = self.packer.device_bucket(("in", kind, sh.index), (n, g.stride), TORCH_DTYPE[g.store_dtype],
+                                                    sh.device)
+                    stack.gather_into(buf)
+                    stack = buf
+                ak = acc_kind_of(kind, g.numerics.mode)
+                acc = self.packer.device_bucket(("acc", kind), (g.stride,), _ACC_TORCH[ak], sh.device)
+                trim_sum_stack(ak, stack, trim, acc, n_clients=n)
+                if self.packer.last_row_tables.get(kind) == "slab":  # the caller's memory, read in place
+                    self.packer.hold([stack], sh.device)
+            sums[kind] = [(sh, FoldedSum(acc, ak, n, sh.width))]
+        return self._finish(plan, self._server_step(plan, sums, server_opt))
 
     # -- the server step of a round: one-launch and streamed rounds alike ------------------------
     def _server_step(self, plan: BucketPlan, sums: dict, server_opt) -> dict:

@@ -284,4 +284,60 @@ inline Plan plan_fold_window(int acc_kind, int64_t ncols, int cus, int forced = 
   return Plan{kFamFoldRows, v, kFoldW, kPieceChunks / (v * kFoldW), 0, 0, false, grid};
 }
 
+// Coordinate-wise trimmed sums (fa_trim_sum): a lane sorts its column's clients in registers, so the
+// kernel is instantiated per padded depth NP, the smallest of 4, 8, ..., 128 that holds n_clients.
+// A block of kTrimW waves owns pieces of 64 * kTrimW consecutive columns (one dword per lane and
+// row) and strides over the window's pieces by the grid; the grid is the pieces, at most the
+// blocks resident at once: CUs x the waves per SIMD the instantiation's registers allow
+// (trim_waves_per_simd, from the compiled VGPR counts in DESIGN.md section 12).
+constexpr int kTrimW = 4;
+constexpr int kTrimMaxClients = FA_TRIM_MAX_CLIENTS;
+
+struct TrimPlan {
+  int np;          // sort slots per lane (0: n_clients out of range)
+  int64_t pieces;  // 64 * kTrimW-column pieces of the window
+  int64_t grid;
+};
+
+inline int trim_np(int n) {
+  if (n < 1 || n > kTrimMaxClients) return 0;
+  int np = 4;
+  while (np < n) np *= 2;
+  return np;
+}
+
+// waves per SIMD (= 4-wave blocks per CU) each instantiation is compiled for and reaches: 226
+// VGPRs at NP = 128, 111 at 64, 53 or fewer below (512 / VGPRs, at most 8); with 3 and 5 the two
+// deep ones spill 10 and 1 registers
+constexpr int trim_waves_per_simd(int np) { return np >= 128 ? 2 : np >= 64 ? 4 : 8; }
+
+inline TrimPlan plan_trim_window(int n_clients, int64_t n_cols, int cus, int forced_grid) {
+  const int np = trim_np(n_clients);
+  const int64_t pieces = ceil_div(n_cols, 64 * kTrimW);
+  int64_t grid = forced_grid > 0 ? forced_grid : (int64_t)cus * trim_waves_per_simd(np ? np : 4);
+  if (grid > pieces) grid = pieces;
+  if (grid < 1) grid = 1;
+  return TrimPlan{np, pieces, grid};
+}
+
+// 8-byte kinds (trim_kernel_elem): grid-stride, one column per lane, at most 4 blocks per CU
+inline int64_t trim_elem_grid(int64_t n_cols, int cus, int forced_grid) {
+  const int64_t blocks = ceil_div(n_cols, 256), cap = forced_grid > 0 ? forced_grid : (int64_t)cus * 4;
+  return blocks < 1 ? 1 : (blocks < cap ? blocks : cap);
+}
+
+// The sorting network of trim_kernel_rows: Batcher's odd-even merge sort on NP = 2^q slots, as
+// layers (p, k) for p = 1, 2, ..., NP/2 and k = p, p/2, ..., 1, each of up to NP/2 independent
+// compare-exchanges.  Candidate m in [0, NP/2) of layer (p, k) is the pair (a, a + k) with
+// a = k % p + 2k * (m / k) + m % k; it is part of the network (`on`) when both slots exist and lie
+// in the same 2p-block.  1,471 exchanges at NP = 128 (bitonic: 1,792).
+struct TrimPair {
+  int a, b;
+  bool on;
+};
+constexpr TrimPair trim_net_pair(int np, int p, int k, int m) {
+  const int a = k % p + 2 * k * (m / k) + m % k, b = a + k;
+  return TrimPair{a, b, b < np && a / (2 * p) == b / (2 * p)};
+}
+
 }  // namespace fa

@@ -13,6 +13,8 @@
 //   * 8-byte kinds (f64 / i64 buckets, small): 4 quads per thread, one row at a time;
 //   * float16 client stacks (fa_reduce_f16): the fp32 one-piece geometry for the same byte width
 //     (plan_f16_window), octs of 8 halves per 16-B load.
+//   * trimmed sums (fa_trim_sum): one column per lane, the clients sorted in registers, one
+//     instantiation per padded depth (plan_trim_window); 8-byte kinds by repeated selection.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -39,7 +41,7 @@ int fail(int code, const char* what) {
   return code;
 }
 
-// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* call launched.  A launch
+// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* / fa_trim_sum call launched.  A launch
 // stores a pointer and two integers; the name is built once per instantiation (a static of its
 // launch site, as resident_blocks_per_cu keeps its occupancy).
 struct LaunchRecord {
@@ -530,6 +532,38 @@ int launch_fold_finish(const A* acc, int64_t n, const Epi<T>& e, hipStream_t s) 
   return launch_check();
 }
 
+// fa_trim_sum: the padded depth NP and the grid come from plan_trim_window
+template <auto... A>
+struct TInst {};  // the naming tags: trim_kernel_rows<NP,W,NT>, trim_kernel_elem<T>
+template <class T>
+struct EInst {};
+int launch_trim_rows(const TrimPlan& p, const float* stack, int64_t stride, int n, int trim, float* acc_out,
+                     int64_t col0, int64_t ncols, hipStream_t s) {
+#define FA_TRIM_ROWS(NP)                                                                                        \
+  case NP:                                                                                                      \
+    FA_LAUNCH_AS(TInst, trim_kernel_rows, (NP, kTrimW, kNT), p.grid, 64 * kTrimW, s, stack, stride, n, trim,    \
+                 acc_out, col0, ncols);                                                                         \
+    return launch_check()
+  switch (p.np) {
+    FA_TRIM_ROWS(4);
+    FA_TRIM_ROWS(8);
+    FA_TRIM_ROWS(16);
+    FA_TRIM_ROWS(32);
+    FA_TRIM_ROWS(64);
+    FA_TRIM_ROWS(128);
+  }
+#undef FA_TRIM_ROWS
+  return no_kernel("trim_kernel_rows");
+}
+
+template <typename T>
+int launch_trim_elem(int64_t grid, const void* stack, int64_t stride, int n, int trim, void* acc_out, int64_t col0,
+                     int64_t ncols, hipStream_t s) {
+  FA_LAUNCH_AS(EInst, trim_kernel_elem, (T), grid, kThreads, s, static_cast<const T*>(stack), stride, n, trim,
+               static_cast<T*>(acc_out), col0, ncols);
+  return launch_check();
+}
+
 // fa_gather_rows*: the shared argument checks (`bad`: the entry's own complaint, checked after
 // them), then one launch(grid, i0) per tile of up to 65535 clients (the grid's y limit)
 template <class F>
@@ -861,6 +895,31 @@ int fa_fold_finish(int32_t acc_kind, int32_t mode, const void* acc, double denom
     case FA_ACC_I64: return go(int64_t{}, double{});
     default: return go(double{}, double{});  // FA_ACC_F32_W64 / FA_ACC_F64 (plain mean only, checked above)
   }
+}
+
+int fa_trim_sum(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients, int32_t trim,
+                void* acc_out, int64_t col_begin, int64_t n_cols, void* stream) {
+  g_last_launch = LaunchRecord{};
+  if (acc_kind != FA_ACC_F32 && acc_kind != FA_ACC_F64 && acc_kind != FA_ACC_I64)
+    return fail(FA_ERR_ARG, "trimmed sums take FA_ACC_F32, FA_ACC_F64 or FA_ACC_I64");
+  if (n_clients < 1) return fail(FA_ERR_ARG, "n_clients must be >= 1");
+  if (n_clients > FA_TRIM_MAX_CLIENTS) return fail(FA_ERR_ARG, "n_clients exceeds FA_TRIM_MAX_CLIENTS (128)");
+  if (trim < 0 || 2 * (int64_t)trim >= n_clients) return fail(FA_ERR_ARG, "trim must satisfy 0 <= 2 * trim < n_clients");
+  if (n_cols < 0 || col_begin < 0 || row_stride < col_begin + n_cols) return fail(FA_ERR_ARG, "bad column window");
+  if (!stack || !acc_out) return fail(FA_ERR_ARG, "null stack or accumulator");
+  if (!aligned_to(stack, 16) || row_stride % 4 != 0 || col_begin % 4 != 0)
+    return fail(FA_ERR_ALIGN, "row window not 16-B aligned (stack, and row_stride / col_begin in units of 4)");
+  if (!aligned_to(acc_out, 16)) return fail(FA_ERR_ALIGN, "accumulator must be 16-B aligned");
+  if (n_cols == 0) return FA_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int forced = g_reduce_grid.load(std::memory_order_relaxed);
+  if (acc_kind == FA_ACC_F32)
+    return launch_trim_rows(plan_trim_window(n_clients, n_cols, device_cus(), forced), static_cast<const float*>(stack),
+                            row_stride, n_clients, trim, static_cast<float*>(acc_out), col_begin, n_cols, s);
+  const int64_t grid = trim_elem_grid(n_cols, device_cus(), forced);
+  if (acc_kind == FA_ACC_F64)
+    return launch_trim_elem<double>(grid, stack, row_stride, n_clients, trim, acc_out, col_begin, n_cols, s);
+  return launch_trim_elem<int64_t>(grid, stack, row_stride, n_clients, trim, acc_out, col_begin, n_cols, s);
 }
 
 int fa_copy(void* dst, const void* src, int64_t nbytes, void* stream) {

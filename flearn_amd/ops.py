@@ -2,7 +2,8 @@
 engine (aggregator.py, streaming.py, serverstate.py) call.
 
 `reduce_stack*` sum, divide and update a client stack in one launch; `fold_stack` adds a chunk of
-clients to a typed accumulator and `fold_finish` divides and updates a finished one.  `StackSum`
+clients to a typed accumulator and `fold_finish` divides and updates a finished one; `trim_sum_stack`
+makes the accumulator of a robust round (per column, the sorted clients' middle values).  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
 """
@@ -257,6 +258,33 @@ def fold_finish(acc_kind: int, mode: int, acc: torch.Tensor, denom: float, n_col
                                  ctypes.byref(epi) if epi is not None else None, _ptr(out32), _ptr(out64),
                                  na.stream_handle(acc.device))
     na.check(rc, "fa_fold_finish")
+
+
+def trim_sum_stack(acc_kind: int, stack: torch.Tensor, trim: int, acc_out: torch.Tensor, *, n_clients: int | None = None,
+                   col_begin: int = 0, n_cols: int | None = None) -> None:
+    """acc_out[c] = the sum, in ascending IEEE totalOrder, of column col_begin + c's n_clients values
+    without its `trim` smallest and `trim` largest (fa_trim_sum), queued on torch's current stream.
+    acc_kind: na.ACC_F32 (fp32 stack, fp32 sums), na.ACC_F64 or na.ACC_I64; the accumulator is what
+    fold_finish takes, with denom = n_clients - 2 * trim for the trimmed mean.  At most
+    na.TRIM_MAX_CLIENTS clients; the result does not depend on the order of the rows."""
+    if acc_kind not in (na.ACC_F32, na.ACC_F64, na.ACC_I64):
+        raise ValueError("trimmed sums take ACC_F32, ACC_F64 or ACC_I64")
+    if not isinstance(stack, torch.Tensor) or stack.dim() != 2 or stack.stride(1) != 1 or not stack.is_cuda:
+        raise ValueError("stack must be a 2-D device tensor with contiguous rows")
+    adt = _ACC_TORCH[acc_kind]
+    if stack.dtype != adt:
+        raise TypeError(f"stack must be {adt} for this accumulator kind, got {stack.dtype}")
+    n, ncols = _check_window(stack.shape, col_begin, n_cols, n_clients)
+    if n > na.TRIM_MAX_CLIENTS:
+        raise ValueError(f"at most {na.TRIM_MAX_CLIENTS} clients, got {n}")
+    if isinstance(trim, bool) or not isinstance(trim, (int, np.integer)) or trim < 0 or 2 * trim >= n:
+        raise ValueError(f"trim must be an integer with 0 <= 2 * trim < n_clients, got {trim!r} for {n} clients")
+    if (not isinstance(acc_out, torch.Tensor) or acc_out.dtype != adt or not acc_out.is_cuda or acc_out.numel() < ncols
+            or not acc_out.is_contiguous() or acc_out.device != stack.device):
+        raise ValueError(f"acc_out must be a contiguous {adt} tensor of at least {ncols} elements on the stack's device")
+    rc = na.lib().fa_trim_sum(acc_kind, stack.data_ptr(), stack.stride(0), n, int(trim), acc_out.data_ptr(), col_begin,
+                              ncols, na.stream_handle(stack.device))
+    na.check(rc, "fa_trim_sum")
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,0 +1,78 @@
+"""Robust aggregation on the MI355X engine: the coordinate-wise trimmed mean and median of Yin et
+al. (ICML 2018).  flearn has no counterpart; both take FedAVG's place (avg.py:11-46), with its
+`client` / `client_receive` and upload format.
+
+Per model element the N clients' values are ordered (IEEE totalOrder, so NaN and inf have a place),
+the `trim` smallest and largest are dropped and the rest are averaged: up to `trim` uploads per
+side that are NaN, inf or scaled leave every element of the global model finite, where one such
+upload poisons FedAVG's weighted mean.  `agg_weight` must be present in each upload, as in
+flearn's upload format, and is NOT used: a client must not be able to buy influence with its own
+weight.  The result does not depend on the order of the uploads.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from .avg import AVG
+
+
+class TrimmedMean(AVG):
+    """Coordinate-wise trimmed mean.  trim: a float in [0, 0.5) is the fraction dropped per side,
+    t = floor(trim * N) each round; an int is the count per side (0 <= 2 t < N is checked per
+    round).  trim = 0 is a mean summed in sorted order, not FedAVG's list-order sum.
+    server_opt: a ServerOptimizer (AVGM / Adagrad / Yogi / Adam) fused into the round's divide,
+    with w_local := the previous global model, as AVGM / OPT(server_side=True) do.
+    At most 128 clients per round, one device, fp32 / float64 / int64 tensors; anything else takes
+    server_exception's route, like any client-data error.  `agg_weight` is required and ignored."""
+
+    def __init__(self, trim=0.1, server_opt=None, encrypt=None, output="reference", device=None, devices=None,
+                 group=None, chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
+        self.trim = self._check_trim(trim)
+        self.server_opt = server_opt
+
+    @staticmethod
+    def _check_trim(trim):
+        if isinstance(trim, (bool, np.bool_)):
+            raise ValueError("trim must be a fraction in [0, 0.5) or a count >= 0, not a bool")
+        if isinstance(trim, (int, np.integer)):
+            if trim < 0:
+                raise ValueError(f"trim count must be >= 0, got {trim}")
+            return int(trim)
+        if isinstance(trim, (float, np.floating)):
+            if not 0.0 <= trim < 0.5:  # NaN fails both
+                raise ValueError(f"trim fraction must be in [0, 0.5), got {trim}")
+            return float(trim)
+        raise ValueError(f"trim must be a float fraction or an int count, got {type(trim).__name__}")
+
+    def trim_count(self, n_clients: int) -> int:
+        """Values dropped per side in a round of n_clients uploads."""
+        if isinstance(self.trim, float):
+            return math.floor(self.trim * n_clients)
+        return self.trim
+
+    def server_ensemble(self, agg_weight_lst, w_local_lst, key_lst=None, server_opt=None):
+        """The engine's robust round (Aggregator.ensemble_trimmed).  agg_weight_lst is checked for
+        presence by server_pre_processing and not used."""
+        return self.engine.ensemble_trimmed(w_local_lst, self.trim_count(len(w_local_lst)), key_lst, server_opt=server_opt)
+
+    def server(self, ensemble_params_lst, round_):
+        """{"w_glob": trimmed mean}; client-data errors -> server_exception, device errors propagate."""
+        return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, server_opt=self.server_opt)}
+
+    def begin_round(self, round_):
+        raise ValueError("a robust round needs every client at once: begin_round() is not supported")
+
+
+class Median(TrimmedMean):
+    """Coordinate-wise median: the trimmed mean with t = (N - 1) // 2, which keeps one value for
+    odd N and the mean of the two middle values for even N.  `agg_weight` is required and ignored."""
+
+    def __init__(self, server_opt=None, encrypt=None, output="reference", device=None, devices=None, group=None,
+                 chunk_clients=None):
+        super().__init__(0, server_opt, encrypt, output, device, devices, group, chunk_clients)
+
+    def trim_count(self, n_clients: int) -> int:
+        return max(0, (n_clients - 1) // 2)

@@ -6,7 +6,7 @@ import random
 import numpy as np
 import torch
 
-from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Prox
+from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Median, Prox, TrimmedMean
 
 __all__ = ["setup_strategy", "setup_seed", "base_strategy_lst", "OUT_OF_SCOPE"]
 
@@ -21,7 +21,7 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     """Name -> strategy instance, as common/utils.py:16-58.  Unknown names fall back to
     `custom_strategy`, else SystemError.  Extra keyword arguments understood here:
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
-    (engine), server_side (AVGM / OPT)."""
+    (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median)."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -38,6 +38,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "opt": lambda: OPT(server_side=server_side, **eng),
         "sgd": lambda: SGD(**eng),
         "prox": lambda: Prox(**eng),
+        "trimmedmean": lambda: TrimmedMean(strategy_p.get("trim", 0.1), strategy_p.get("server_opt"), **eng),
+        "median": lambda: Median(strategy_p.get("server_opt"), **eng),
     }
     if name in factories:
         return factories[name]()

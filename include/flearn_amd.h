@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 17
+#define FA_ABI_VERSION 18
 
 /* return codes */
 #define FA_OK 0
@@ -270,7 +270,7 @@ int fa_set_reduce_grid(int32_t grid);
 int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
- * _i64 / _f16 / fa_fold / fa_fold_finish call launched.  For tests and profilers that must know which kernel instantiation a
+ * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -328,6 +328,28 @@ int fa_fold(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_c
  * aligned, the per-column arrays as for fa_reduce_f32 (FA_ERR_ALIGN).  n_cols == 0 is a no-op.  */
 int fa_fold_finish(int32_t acc_kind, int32_t mode, const void* acc, double denom, int64_t n_cols,
                    const fa_epilogue* epi, float* out32, double* out64, void* stream);
+
+/* ---- robust aggregation: coordinate-wise trimmed sums -------------------
+ * The trimmed mean and the median of Yin et al. (ICML 2018).  There is no reference counterpart:
+ * the nearest is the weighted mean of flearn/common/strategy/strategy.py:123-129, whose place in
+ * Strategy.server these take.  Per column the n_clients values are ordered by IEEE totalOrder
+ * (-NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN; int64 as integers), the `trim` smallest and
+ * the `trim` largest are dropped, and the rest are summed in ascending order in the kind's sum
+ * type, the first kept value initialising the sum (no fused multiply-add, int64 wraps).  The
+ * result does not depend on the order of the rows.  The median is trim = (n_clients - 1) / 2.
+ * ABI 18.                                                                                        */
+#define FA_TRIM_MAX_CLIENTS 128
+/* acc_out[c] = sum, in ascending totalOrder, of the n_clients - 2*trim middle values of column
+ * col_begin + c.  acc_kind: FA_ACC_F32 (float rows -> float sums), FA_ACC_F64, FA_ACC_I64;
+ * FA_ACC_F32_W64 and unknown kinds: FA_ERR_ARG.  The accumulator is what fa_fold_finish takes
+ * (with denom = n_clients - 2*trim it gives the trimmed mean).  FA_ERR_ARG for n_clients < 1,
+ * n_clients > FA_TRIM_MAX_CLIENTS, trim < 0 or 2*trim >= n_clients; FA_ERR_ALIGN for a stack or
+ * acc_out that is not 16-byte aligned or a col_begin / row_stride that is not a multiple of 4
+ * elements, as for fa_fold.  Every error is decided before any HIP call.  Nothing outside
+ * acc_out[0, n_cols) is written; n_cols == 0 is a no-op.  fa_set_reduce_grid applies;
+ * fa_last_launch names the instantiation, e.g. "trim_kernel_rows<128,4,true>".               */
+int fa_trim_sum(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients,
+                int32_t trim, void* acc_out, int64_t col_begin, int64_t n_cols, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

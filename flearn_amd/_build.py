@@ -4,13 +4,16 @@ from __future__ import annotations
 import os
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
-SOURCES = [HERE / "csrc" / "fa_reduce.hip"]
+# the device units, one per entry group (each includes only the kernel families it launches)
+SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport")]
 HOST_SOURCES = [HERE / "csrc" / "fa_wire.cpp"]  # plain host C++ (g++), linked into the same .so
-DEPS = [HERE / "csrc" / "fa_device.hpp", HERE / "csrc" / "fa_geometry.hpp"]
+DEPS = sorted((HERE / "csrc").glob("*.hpp"))  # every header: a new one cannot be forgotten
+MAX_COMPILE_JOBS = 8
 HEADERS = [REPO / "include" / "flearn_amd.h"]
 OUT = HERE / "lib" / "libflearn_amd.so"
 PYHOST_SOURCE = HERE / "csrc" / "fa_pyhost.c"  # Python-object pack helper (ctypes.PyDLL), not C ABI
@@ -115,6 +118,11 @@ def build_torchmeta(force: bool = False, verbose: bool = False):
     return TORCHMETA_OUT
 
 
+def object_of(src: Path) -> Path:
+    """Where build_native leaves a unit's object: beside the library."""
+    return OUT.parent / (src.stem + ".o")
+
+
 def build_native(force: bool = False, verbose: bool = False) -> Path:
     build_pyhost(force, verbose)
     build_torchmeta(force, verbose)
@@ -123,18 +131,18 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
         return OUT
     OUT.parent.mkdir(parents=True, exist_ok=True)
     tmp = OUT.with_suffix(".so.tmp")
-    objs = []
-    for src in HOST_SOURCES:
-        obj = OUT.parent / (src.stem + ".o")
+    shared = max(p.stat().st_mtime for p in DEPS + HEADERS + [Path(__file__)])
+
+    def stale(src):  # a unit is compiled again when it, any header or this file is newer than its object
+        obj = object_of(src)
+        return force or not obj.exists() or obj.stat().st_mtime < max(src.stat().st_mtime, shared)
+
+    jobs = []  # the stale units' compile commands; they run side by side, then one link
+    for src in filter(stale, HOST_SOURCES):
         hcmd = [os.environ.get("CXX", "g++"), "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wall",
-                f"-I{REPO / 'include'}", "-c", str(src), "-o", str(obj)]
-        if verbose:
-            print(" ".join(hcmd))
-        subprocess.run(hcmd, check=True)
-        objs.append(str(obj))
-    dev_objs = []
-    for src in SOURCES:  # device code: compile, then link with the host objects
-        obj = OUT.parent / (src.stem + ".o")
+                f"-I{REPO / 'include'}", "-c", str(src), "-o", str(object_of(src))]
+        jobs.append(hcmd)
+    for src in filter(stale, SOURCES):  # device code
         cmd = [
             hipcc(),
             f"--offload-arch={ARCH}",
@@ -147,13 +155,16 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
             "-c",
             str(src),
             "-o",
-            str(obj),
+            str(object_of(src)),
         ]
-        if verbose:
+        jobs.append(cmd)
+    if verbose:
+        for cmd in jobs:
             print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
-        dev_objs.append(str(obj))
-    link = [hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", "-pthread", "-o", str(tmp), *dev_objs, *objs]
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs), MAX_COMPILE_JOBS))) as pool:
+        list(pool.map(lambda cmd: subprocess.run(cmd, check=True), jobs))  # raises the first failure
+    link = [hipcc(), f"--offload-arch={ARCH}", "-fPIC", "-shared", "-pthread", "-o", str(tmp),
+            *(str(object_of(src)) for src in SOURCES + HOST_SOURCES)]
     if verbose:
         print(" ".join(link))
     subprocess.run(link, check=True)

@@ -314,7 +314,7 @@ void ora_update_dyn_f32(const float* g, float* h, float* theta, double nclients_
   }
 }
 
-/* ---- synthetic generator, identical to the device fill (flearn_amd/csrc/fa_reduce.hip) ---- */
+/* ---- synthetic generator, identical to the device fill (flearn_amd/csrc/fa_transport.hpp) ---- */
 static uint64_t splitmix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

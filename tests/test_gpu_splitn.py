@@ -23,7 +23,7 @@ from golden_io import bitwise_equal
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-6  # north star: "within 1e-6 relative per fp32 tensor"
-SPLIT_MAX_N = 256  # kSplitMaxN (flearn_amd/csrc/fa_reduce.hip)
+SPLIT_MAX_N = 256  # kSplitMaxN (flearn_amd/csrc/fa_geometry.hpp)
 
 
 def _uses_split(n, p):

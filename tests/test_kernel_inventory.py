@@ -55,10 +55,11 @@ def normalise(symbol_line):
 
 
 def shipped_instantiations():
-    obj = na.LIB_PATH.parent / "fa_reduce.o"  # build_native leaves it beside the library
-    binary = obj if obj.exists() else na.LIB_PATH
-    assert binary.exists(), f"{binary} not built: run __graft_entry__.build()"
-    out = subprocess.run(symbol_lister() + [str(binary)], capture_output=True, text=True, check=True).stdout
+    objs = [_build.object_of(src) for src in _build.SOURCES]  # build_native leaves them beside the library
+    binaries = objs if all(o.exists() for o in objs) else [na.LIB_PATH]
+    for binary in binaries:
+        assert binary.exists(), f"{binary} not built: run __graft_entry__.build()"
+    out = subprocess.run(symbol_lister() + [str(b) for b in binaries], capture_output=True, text=True, check=True).stdout
     # the host stub (__device_stub__...) and the kernel handle demangle to the same template-id
     return {n for n in map(normalise, out.splitlines()) if n}
 

@@ -11,4 +11,5 @@
 #include "fa_half.hpp"
 #include "fa_fold.hpp"
 #include "fa_trim.hpp"
+#include "fa_gram.hpp"
 #include "fa_transport.hpp"

@@ -1,4 +1,5 @@
-// fa_geometry.hpp — which reduce kernel instantiation runs for a shape, and on what grid.
+// fa_geometry.hpp — which kernel instantiation runs for a shape, and on what grid: the reduces, the
+// folds, the trimmed sums and the Gram matrix.
 //
 // Plain C++17, pure integer decisions: no HIP, no globals, no device queries.  fa_reduce.hip asks
 // these functions for a Plan and turns it into a launch; tests/geometry_probe.cpp asks them on a
@@ -324,6 +325,54 @@ inline TrimPlan plan_trim_window(int n_clients, int64_t n_cols, int cus, int for
 inline int64_t trim_elem_grid(int64_t n_cols, int cus, int forced_grid) {
   const int64_t blocks = ceil_div(n_cols, 256), cap = forced_grid > 0 ? forced_grid : (int64_t)cus * 4;
   return blocks < 1 ? 1 : (blocks < cap ? blocks : cap);
+}
+
+// The client Gram matrix (fa_gram_f32): G = Y Y^T over a column window, on
+// v_mfma_f32_32x32x2_f32.  The kernel is instantiated per padded depth NP, the smallest multiple of
+// the 32-row MFMA tile that holds n_clients (32, 64, 96, 128).  A block of 4 waves owns one
+// contiguous share of the window, in whole LDS chunks of Kc columns (Kc by NP so that the
+// double-buffered tile fills the LDS: gram_kc), the chunks spread evenly over the grid (block b:
+// chunks [b * chunks / grid, (b + 1) * chunks / grid)); one block per CU at most, since one tile
+// pair takes most of a CU's LDS.  Every kGramLc columns (whole chunks) the MFMA accumulators (the
+// inner chain) are added into a second fp32 tile in registers and cleared, so the longest sequence
+// of fp32 roundings behind one entry of a block's partial is chain = Lc + ceil(share / Lc): at most
+// Lc products in the inner chain, then one add per inner tile.  (A wave sums only its 1/KS of each
+// chunk's columns, and the KS waves' tiles are added at the block's end: Lc / KS + ceil(share / Lc)
+// + KS - 1 roundings, which is below `chain` for KS in {2, 4}.)  The natural grid keeps
+// chain <= 8192 for windows up to 2^25 columns on 64 CUs or more (share <= 2^19 + Kc).
+constexpr int kGramMaxClients = FA_GRAM_MAX_CLIENTS;
+constexpr int kGramTile = 32;
+constexpr int kGramLc = 1024;
+
+struct GramPlan {
+  int np;           // padded clients (0: n_clients out of range)
+  int kc;           // columns per LDS chunk
+  int lc;           // columns per inner chain
+  int64_t chunks;   // Kc-column chunks of the window
+  int64_t grid;     // blocks = partial tiles in the workspace
+  int64_t share;    // the widest block's columns (whole chunks)
+  int64_t chain;    // lc + ceil(share / lc)
+  int64_t workspace_bytes;  // grid * np * np * 4
+};
+
+inline int gram_np(int n) {
+  if (n < 1 || n > kGramMaxClients) return 0;
+  return (n + kGramTile - 1) / kGramTile * kGramTile;
+}
+
+// NP * Kc = 16 Ki floats (96: 12 Ki): two [NP][Kc + 4] fp32 tiles are 132-135 KiB (96: 99) of LDS
+constexpr int gram_kc(int np) { return np <= 32 ? 512 : np <= 64 ? 256 : 128; }
+
+inline GramPlan plan_gram_window(int n_clients, int64_t n_cols, int cus, int forced_grid) {
+  const int np = gram_np(n_clients);
+  const int kc = gram_kc(np ? np : kGramTile);
+  const int64_t chunks = ceil_div(n_cols < 1 ? 1 : n_cols, kc);
+  int64_t grid = forced_grid > 0 ? forced_grid : cus;
+  if (grid > chunks) grid = chunks;
+  if (grid < 1) grid = 1;
+  const int64_t share = ceil_div(chunks, grid) * kc;
+  return GramPlan{np, kc, kGramLc, chunks, grid, share, kGramLc + ceil_div(share, kGramLc),
+                  grid * (int64_t)(np ? np : kGramTile) * (np ? np : kGramTile) * 4};
 }
 
 // The sorting network of trim_kernel_rows: Batcher's odd-even merge sort on NP = 2^q slots, as

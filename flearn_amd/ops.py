@@ -287,6 +287,57 @@ def trim_sum_stack(acc_kind: int, stack: torch.Tensor, trim: int, acc_out: torch
     na.check(rc, "fa_trim_sum")
 
 
+def gram_workspace(n_clients: int, n_cols: int) -> int:
+    """Bytes of workspace gram_stack needs for this shape (fa_gram_workspace): enough on any device
+    and under any set_reduce_grid."""
+    need = na.load().fa_gram_workspace(int(n_clients), int(n_cols))
+    if need < 0:
+        na.check(int(need), "fa_gram_workspace")
+    return int(need)
+
+
+def gram_stack(stack: torch.Tensor, *, center: torch.Tensor | None = None, n_clients: int | None = None,
+               col_begin: int = 0, n_cols: int | None = None, out: torch.Tensor | None = None,
+               workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """The clients' Gram matrix over the window [col_begin, +n_cols) of an fp32 stack (fa_gram_f32),
+    queued on torch's current stream: G[i, j] = sum_k y_i[k] * y_j[k] with y_i = fl32(x_i - center),
+    a float64 [N, N] device tensor, symmetric bit for bit.  center: an fp32 device row laid out like
+    a stack row (indexed by the stack's columns, at least col_begin + n_cols long), or None.  At most
+    na.GRAM_MAX_CLIENTS clients.  out: a contiguous float64 tensor of at least N * N elements to
+    write (else a fresh one); workspace: a 16-B aligned device buffer of at least
+    gram_workspace(N, n_cols) bytes (else a fresh one)."""
+    if not isinstance(stack, torch.Tensor) or stack.dim() != 2 or stack.stride(1) != 1 or not stack.is_cuda:
+        raise ValueError("stack must be a 2-D device tensor with contiguous rows")
+    if stack.dtype != torch.float32:
+        raise TypeError(f"stack must be torch.float32, got {stack.dtype}")
+    n, ncols = _check_window(stack.shape, col_begin, n_cols, n_clients)
+    if n > na.GRAM_MAX_CLIENTS:
+        raise ValueError(f"at most {na.GRAM_MAX_CLIENTS} clients, got {n}")
+    if ncols < 1:
+        raise ValueError("the column window is empty")
+    if center is not None:
+        if (not isinstance(center, torch.Tensor) or center.dtype != torch.float32 or center.device != stack.device
+                or center.dim() != 1 or not center.is_contiguous() or center.numel() < col_begin + ncols):
+            raise ValueError(f"center must be a contiguous 1-D torch.float32 tensor of at least {col_begin + ncols} "
+                             "elements on the stack's device")
+    if out is None:
+        out = torch.empty((n, n), dtype=torch.float64, device=stack.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != stack.device
+          or not out.is_contiguous() or out.numel() < n * n):
+        raise ValueError(f"out must be a contiguous torch.float64 tensor of at least {n * n} elements on the stack's device")
+    need = gram_workspace(n, ncols)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=stack.device)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != stack.device or not workspace.is_contiguous()
+          or workspace.numel() * workspace.element_size() < need):
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on the stack's device")
+    rc = na.lib().fa_gram_f32(stack.data_ptr(), stack.stride(0), n, _ptr(center), col_begin, ncols, workspace.data_ptr(),
+                              workspace.numel() * workspace.element_size(), out.data_ptr(),
+                              na.stream_handle(stack.device))
+    na.check(rc, "fa_gram_f32")
+    return out.reshape(-1)[: n * n].view(n, n)
+
+
 # ---------------------------------------------------------------------------------------------
 # a round's weighted sum, either way: what the engine's server step divides and updates
 # ---------------------------------------------------------------------------------------------

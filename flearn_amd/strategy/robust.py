@@ -1,5 +1,6 @@
 """Robust aggregation on the MI355X engine: the coordinate-wise trimmed mean and median of Yin et
-al. (ICML 2018).  flearn has no counterpart; both take FedAVG's place (avg.py:11-46), with its
+al. (ICML 2018), and Krum / multi-Krum of Blanchard et al. (NeurIPS 2017), which judges whole uploads
+(below).  flearn has no counterpart; all take FedAVG's place (avg.py:11-46), with its
 `client` / `client_receive` and upload format.
 
 Per model element the N clients' values are ordered (IEEE totalOrder, so NaN and inf have a place),
@@ -14,6 +15,7 @@ from __future__ import annotations
 import math
 
 import numpy as np
+import torch
 
 from .avg import AVG
 
@@ -76,3 +78,70 @@ class Median(TrimmedMean):
 
     def trim_count(self, n_clients: int) -> int:
         return max(0, (n_clients - 1) // 2)
+
+
+class MultiKrum(AVG):
+    """Multi-Krum (Blanchard et al., NeurIPS 2017): with up to f bad uploads among N, an upload's
+    score is the sum of its squared distances to its N - f - 2 nearest other uploads; the m uploads
+    of lowest score are averaged with equal weights and the others are left out whole.  The engine's
+    audit of a round is `self.engine.last_krum` ("selected": who was kept, in upload order).
+    f: ints only, N >= 2 f + 3 is checked per round; m: None = N - f per round, else 1 <= m <= N - f.
+    center: "previous" (the default) subtracts this strategy's own last w_glob (a copy it keeps) from
+    every upload before the distances are taken — models of one round are g + delta with
+    |delta| << |g|, and G_ii + G_jj - 2 G_ij of uncentred rows cancels to a few digits, while
+    fl32(x - g) is nearly exact and distances do not depend on the centre; the first round runs
+    uncentred.  None never centres.  The centre is the server's own state, never a client's row.
+    server_opt: a ServerOptimizer fused into the divide, as for TrimmedMean.  Distances are measured
+    on the fp32 tensors only (int64 / float64 buffers such as BN counters do not enter them).  At
+    most 128 clients per round, one device; more than f non-finite uploads, like any client-data
+    error, take server_exception's route.  `agg_weight` is required and ignored: a client must not be
+    able to buy influence with its own weight."""
+
+    def __init__(self, f, m=None, server_opt=None, center="previous", encrypt=None, output="reference", device=None,
+                 devices=None, group=None, chunk_clients=None):
+        super().__init__(encrypt, output, device, devices, group, chunk_clients)
+        self.f = self._check_count("f", f, 0)
+        self.m = None if m is None else self._check_count("m", m, 1)
+        if center is not None and center != "previous":
+            raise ValueError(f'center must be "previous" or None, got {center!r}')
+        self.center = center
+        self.server_opt = server_opt
+        self._prev_glob = None
+
+    @staticmethod
+    def _check_count(name, v, lo):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"{name} must be an int >= {lo}, got {v!r}")
+        return int(v)
+
+    def select_count(self, n_clients: int) -> int:
+        """Uploads averaged in a round of n_clients."""
+        return n_clients - self.f if self.m is None else self.m
+
+    def server_ensemble(self, agg_weight_lst, w_local_lst, key_lst=None, server_opt=None):
+        """The engine's Krum round (Aggregator.ensemble_krum).  agg_weight_lst is checked for presence
+        by server_pre_processing and not used."""
+        center = self._prev_glob if self.center == "previous" else None
+        w_glob = self.engine.ensemble_krum(w_local_lst, self.f, self.select_count(len(w_local_lst)), key_lst,
+                                           server_opt=server_opt, center=center)
+        if self.center == "previous":  # a copy of its own: the caller may change what it is handed
+            self._prev_glob = {k: v.detach().clone() if isinstance(v, torch.Tensor) else np.array(v)
+                               for k, v in w_glob.items()}
+        return w_glob
+
+    def server(self, ensemble_params_lst, round_):
+        """{"w_glob": mean of the selected uploads}; client-data errors -> server_exception, device
+        errors propagate."""
+        return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, server_opt=self.server_opt)}
+
+    def begin_round(self, round_):
+        raise ValueError("a robust round needs every client at once: begin_round() is not supported")
+
+
+class Krum(MultiKrum):
+    """Krum: the one upload of lowest score becomes the global model (MultiKrum with m = 1).
+    `agg_weight` is required and ignored."""
+
+    def __init__(self, f, server_opt=None, center="previous", encrypt=None, output="reference", device=None,
+                 devices=None, group=None, chunk_clients=None):
+        super().__init__(f, 1, server_opt, center, encrypt, output, device, devices, group, chunk_clients)

@@ -6,7 +6,7 @@ import random
 import numpy as np
 import torch
 
-from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Median, Prox, TrimmedMean
+from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, Prox, TrimmedMean
 
 __all__ = ["setup_strategy", "setup_seed", "base_strategy_lst", "OUT_OF_SCOPE"]
 
@@ -21,7 +21,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     """Name -> strategy instance, as common/utils.py:16-58.  Unknown names fall back to
     `custom_strategy`, else SystemError.  Extra keyword arguments understood here:
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
-    (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median)."""
+    (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median),
+    f, m, center and server_opt (Krum / MultiKrum; f defaults to 0)."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -40,6 +41,9 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "prox": lambda: Prox(**eng),
         "trimmedmean": lambda: TrimmedMean(strategy_p.get("trim", 0.1), strategy_p.get("server_opt"), **eng),
         "median": lambda: Median(strategy_p.get("server_opt"), **eng),
+        "krum": lambda: Krum(strategy_p.get("f", 0), strategy_p.get("server_opt"), strategy_p.get("center", "previous"), **eng),
+        "multikrum": lambda: MultiKrum(strategy_p.get("f", 0), strategy_p.get("m"), strategy_p.get("server_opt"),
+                                       strategy_p.get("center", "previous"), **eng),
     }
     if name in factories:
         return factories[name]()

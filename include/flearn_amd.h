@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 18
+#define FA_ABI_VERSION 19
 
 /* return codes */
 #define FA_OK 0
@@ -270,7 +270,7 @@ int fa_set_reduce_grid(int32_t grid);
 int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
- * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum call launched.  For tests and profilers that must know which kernel instantiation a
+ * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -350,6 +350,38 @@ int fa_fold_finish(int32_t acc_kind, int32_t mode, const void* acc, double denom
  * fa_last_launch names the instantiation, e.g. "trim_kernel_rows<128,4,true>".               */
 int fa_trim_sum(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients,
                 int32_t trim, void* acc_out, int64_t col_begin, int64_t n_cols, void* stream);
+
+/* ---- robust aggregation: the client Gram matrix (Krum / multi-Krum) -------
+ * Blanchard et al. (NeurIPS 2017) judge whole uploads by their squared distances to the others;
+ * all of them come from the n_clients x n_clients Gram matrix of the clients' rows.  There is no
+ * reference counterpart: the rule takes the place of the weighted mean of
+ * flearn/common/strategy/strategy.py:123-129 in Strategy.server.  ABI 19.                        */
+#define FA_GRAM_MAX_CLIENTS 128
+/* Bytes of workspace fa_gram_f32 needs for this shape on any device and under any
+ * fa_set_reduce_grid (at most 512 partial tiles of NP x NP floats, NP = n_clients rounded up to
+ * 32); FA_ERR_ARG for n_clients outside [1, FA_GRAM_MAX_CLIENTS] or n_cols < 1.  HOST function,
+ * no HIP call.                                                                                   */
+int64_t fa_gram_workspace(int32_t n_clients, int64_t n_cols);
+/* gram_out[i * n_clients + j] = sum over the window's columns k of y_i[k] * y_j[k], where
+ * y_i[k] = fl32(stack[i][col_begin + k] - center[col_begin + k]) (one fp32 subtract; center: an
+ * fp32 row laid out like a stack row, 16-byte aligned, NULL: y = x).  Products and sums are exact
+ * fp32 fused multiply-adds on the matrix cores in a fixed order, folded into fp32 partial tiles
+ * (one per block, in `workspace`) and summed per entry in float64 in block order by a second
+ * kernel: the same inputs on the same device and grid give the same bits, gram_out is symmetric
+ * bit for bit, and |error| <= (gamma(chain) + grid * 2^-52) * sum_k |y_i[k] y_j[k]| with chain
+ * and grid from plan_gram_window (csrc/fa_geometry.hpp; chain <= 8192 on the natural grid for
+ * n_cols <= 2^25).  A non-finite value in row i makes row i and column i of gram_out non-finite and
+ * nothing else.  FA_ERR_ARG for a null stack / workspace / gram_out, n_clients outside
+ * [1, FA_GRAM_MAX_CLIENTS], n_cols < 1 or a window outside the row; FA_ERR_ALIGN as for fa_fold
+ * (stack, center, workspace 16-byte aligned, gram_out 8, row_stride / col_begin multiples of 4
+ * elements); FA_ERR_SIZE for workspace_bytes < fa_gram_workspace (fa_last_error names the
+ * size).  Every error is decided before any HIP call.  Nothing outside gram_out[0, n_clients^2)
+ * and the workspace is written; nothing is allocated or synchronised.  fa_set_reduce_grid
+ * applies (at most 512 blocks); fa_last_launch names the tile kernel's instantiation and grid,
+ * e.g. "gram_kernel_tile<128,true,true>", launches = 2.                                         */
+int fa_gram_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
+                int64_t col_begin, int64_t n_cols, void* workspace, int64_t workspace_bytes,
+                double* gram_out, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

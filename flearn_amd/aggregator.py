@@ -5,10 +5,9 @@ flearn/common/strategy/strategy.py:102-130: plan the buckets (bucketplan.py), co
 HBM, run ONE fused reduce launch per bucket kind on torch's current stream, and hand back a
 fresh dict with the reference's value types.  `begin_round` aggregates the same round in chunks of
 clients (streaming.py); both end in the same server step (`Aggregator._server_step`), fed by
-either kind of weighted sum (ops.StackSum, ops.FoldedSum).  `ensemble_trimmed` is the robust round:
-coordinate-wise trimmed sums (ops.trim_sum_stack) into the same server step.  `ensemble_krum` is the
-per-client robust round: the clients' Gram matrix (ops.gram_stack), krum.krum_select on the host, and
-the selected uploads' mean from the stacks already on the device.
+either kind of weighted sum (ops.StackSum, ops.FoldedSum).  The robust rounds, `ensemble_trimmed`
+(coordinate-wise trimmed mean and median) and `ensemble_krum` (Krum / multi-Krum), are
+robustround.py's, bound on the class; they end in the same server step.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
 (`ServerOptimizer`, `DynState`) serverstate.py, the small-host-round fast path smallround.py; every
@@ -16,20 +15,17 @@ name this module defined before it was split is re-exported here as the same obj
 """
 from __future__ import annotations
 
-import dataclasses
-
 import numpy as np
 import torch
 
 from . import _native as na
-from . import krum, smallround
-from .bucketplan import TORCH_DTYPE, BucketPlan, Group, Shard, make_plan, rank_width, select_keys
+from . import robustround, smallround
+from .bucketplan import BucketPlan, Shard, key_runs, make_plan, rank_width, select_keys  # noqa: F401
 from .dist import gather_columns
 from .ops import (FoldedSum, StackSum, _byte_range, _check_arrays, _check_cuda, _check_stack, _check_v_out,  # noqa: F401
                   _check_weights, _check_window, _epilogue, _ptr, _reduce_stack8, apply_dyn, apply_update, fill_uniform,
                   last_launch, mean_tables, reduce_stack, reduce_stack_f16, reduce_stack_f64, reduce_stack_i64,
                   set_reduce_grid)
-from .ops import _ACC_TORCH, acc_kind_of, gram_stack, gram_workspace, trim_sum_stack
 from .packer import Packer
 from .rowtable import RowTable
 from .semantics import KIND_F16, KIND_F32, Numerics
@@ -73,6 +69,12 @@ class Aggregator:
     #: _small_round(plan, w_local_lst): the small-host-round fast path (smallround.py), bound here as
     #: a method so the server call pays no extra Python call for the split
     _small_round = smallround._small_round
+    #: the robust rounds (robustround.py), bound the same way; last_krum: the last Krum round's audit
+    ensemble_trimmed = robustround.ensemble_trimmed
+    ensemble_krum = robustround.ensemble_krum
+    _check_center = staticmethod(robustround._check_center)
+    _center_row = robustround._center_row
+    last_krum = None
 
     def __init__(self, device=None, output: str = "reference", workers: int = 8, devices=None, group=None,
                  reorder: bool = False, chunk_clients: int | None = None):
@@ -158,215 +160,10 @@ class Aggregator:
         stacks = self.packer.pack(plan, w_local_lst)
         results = self._server_step(plan, stacks, server_opt)
         for kind, parts in stacks.items():
-            if self.packer.last_row_tables.get(kind) == "slab":  # the caller's memory, read in place:
-                self.packer.hold([st for _, st in parts], parts[0][0].device)  # alive until read
+            self.packer.hold_slab(kind, [st for _, st in parts], parts[0][0].device)
         if self._dist and KIND_F32 in results:
             results[KIND_F32] = self._gather_columns(plan, results[KIND_F32])
         return self._finish(plan, results)
-
-    # -- robust rounds: coordinate-wise trimmed mean and median ----------------------------------
-    def ensemble_trimmed(self, w_local_lst, trim: int, key_lst=None, server_opt: ServerOptimizer | None = None):
-        """The coordinate-wise trimmed mean of the uploads (Yin et al., ICML 2018): per element, the
-        N clients' values in IEEE totalOrder, the `trim` smallest and the `trim` largest dropped, the
-        rest summed in ascending order in the bucket's sum type and divided by N - 2 * trim (the
-        median is trim = (N - 1) // 2).  There are no weights: a client cannot buy influence with
-        its own agg_weight, and the result does not depend on the order of the uploads.  The plan is
-        make_plan's for Python-int weights (key intersection, layouts and errors as in `ensemble`),
-        the uploads are packed as ever (host, device, slab), fa_trim_sum makes each bucket's sums,
-        and the server step — the divide, a fused AVGM / OPT update, the three output modes — is
-        the one a streamed round ends in.
-
-        Refused before anything is queued: float16 buckets and FedDyn state (TypeError: its h
-        update needs the plain sum over all N); several devices, group= and chunk_clients
-        (ValueError: every client must be present for a column's order statistics); more than
-        128 clients and a trim outside 0 <= 2 * trim < N (ValueError)."""
-        if self.chunk_clients is not None:
-            raise ValueError("a robust round needs every client at once: chunk_clients is not supported")
-        if self._dist:
-            raise ValueError("a robust round is not sharded over a process group (group=)")
-        if len(self.devices) > 1:
-            raise ValueError("a robust round runs on one device: devices=[...] with several devices is not supported")
-        if isinstance(server_opt, DynState):
-            raise TypeError("FedDyn's h update needs the plain sum over all clients: no robust round with Dyn state")
-        n = len(w_local_lst)
-        if n > na.TRIM_MAX_CLIENTS:
-            raise ValueError(f"a robust round takes at most {na.TRIM_MAX_CLIENTS} clients, got {n}")
-        plan = make_plan([1] * n, w_local_lst, key_lst)
-        if KIND_F16 in plan.groups:
-            raise TypeError("float16 uploads: a robust round aggregates fp32 / float64 / int64 buckets only")
-        if isinstance(trim, bool) or not isinstance(trim, (int, np.integer)) or trim < 0 or 2 * trim >= n:
-            raise ValueError(f"trim must be an integer with 0 <= 2 * trim < {n} clients, got {trim!r}")
-        trim = int(trim)
-        # the divide is by the kept count (the plan is make_plan's cached one: a copy carries it)
-        groups = {kind: Group(kind, dataclasses.replace(g.numerics, denom=float(n - 2 * trim)), g.segments, g.stride)
-                  for kind, g in plan.groups.items()}
-        plan = dataclasses.replace(plan, groups=groups)
-        self.last_plan = plan
-        stacks = self.packer.pack(plan, w_local_lst)
-        sums = {}
-        for kind, parts in stacks.items():
-            g = plan.groups[kind]
-            ((sh, stack),) = parts
-            with torch.cuda.device(sh.device):
-                if isinstance(stack, RowTable):  # device uploads: the one-launch gather into the stack
-                    buf = self.packer.device_bucket(("in", kind, sh.index), (n, g.stride), TORCH_DTYPE[g.store_dtype],
-                                                    sh.device)
-                    stack.gather_into(buf)
-                    stack = buf
-                ak = acc_kind_of(kind, g.numerics.mode)
-                acc = self.packer.device_bucket(("acc", kind), (g.stride,), _ACC_TORCH[ak], sh.device)
-                trim_sum_stack(ak, stack, trim, acc, n_clients=n)
-                if self.packer.last_row_tables.get(kind) == "slab":  # the caller's memory, read in place
-                    self.packer.hold([stack], sh.device)
-            sums[kind] = [(sh, FoldedSum(acc, ak, n, sh.width))]
-        return self._finish(plan, self._server_step(plan, sums, server_opt))
-
-    # -- robust rounds: Krum / multi-Krum ---------------------------------------------------------
-    def ensemble_krum(self, w_local_lst, f: int, m: int, key_lst=None, server_opt: ServerOptimizer | None = None,
-                      center=None):
-        """Multi-Krum (Blanchard et al., NeurIPS 2017; Krum is m = 1): the m uploads closest to their
-        N - f - 2 nearest neighbours are averaged, the others are left out whole, and `last_krum`
-        says which.  The uploads are planned (make_plan for Python-int weights) and packed as ever
-        (host, device, slab); the fp32 bucket's client Gram matrix (ops.gram_stack, centred on
-        `center`) goes to the host (8 N^2 bytes per run of keys), krum.krum_select picks the uploads,
-        and their mean is taken from the device stacks already there — the fp32 bucket through a
-        row table of the selected rows' addresses, the 8-byte buckets gathered into a compact stack
-        — with unit weights, in upload order: bit-identical to
-        ensemble([1] * m, [the selected uploads in upload order], the round's keys, server_opt) — the keys
-        common to all N uploads (or key_lst), in the round's order, whoever is selected.
-
-        Distances are measured on the fp32 bucket only: float64 / int64 values (BN counters and the
-        like) do not enter them, and are averaged over the selected clients like the rest.
-        center: a w_glob-like dict (the server's own state, never a client's upload); its fp32 keys
-        are laid out into one fp32 row and subtracted from every upload before the products, which
-        keeps the cancellation in G_ii + G_jj - 2 G_ij harmless for models that differ little.
-
-        self.last_krum = {"gram", "scores", "selected", "centered"} (host arrays) is the audit.
-        Refused before anything is queued: float16 buckets and FedDyn state (TypeError); several
-        devices, group=, chunk_clients, more than 128 clients, bad f / m, and uploads without an
-        fp32 bucket to measure distances on (ValueError).  More than f non-finite uploads: ValueError
-        after the Gram."""
-        if self.chunk_clients is not None:
-            raise ValueError("a robust round needs every client at once: chunk_clients is not supported")
-        if self._dist:
-            raise ValueError("a robust round is not sharded over a process group (group=)")
-        if len(self.devices) > 1:
-            raise ValueError("a robust round runs on one device: devices=[...] with several devices is not supported")
-        if isinstance(server_opt, DynState):
-            raise TypeError("FedDyn's h update needs the plain sum over all clients: no robust round with Dyn state")
-        n = len(w_local_lst)
-        if n > na.GRAM_MAX_CLIENTS:
-            raise ValueError(f"a Krum round takes at most {na.GRAM_MAX_CLIENTS} clients, got {n}")
-        plan = make_plan([1] * n, w_local_lst, key_lst)
-        if KIND_F16 in plan.groups:
-            raise TypeError("float16 uploads: a robust round aggregates fp32 / float64 / int64 buckets only")
-        f, m = krum.check_counts(n, f, m)
-        g32 = plan.groups.get(KIND_F32)
-        if g32 is None or not any(s.numel > 0 for s in g32.segments):
-            raise ValueError("Krum measures distances on the fp32 bucket, and these uploads have none")
-        centre = self._check_center(g32, center)  # refused here, before anything is queued
-        self.last_plan = plan
-        self.last_krum = None
-        stacks = self.packer.pack(plan, w_local_lst)
-        dense = {}
-        for kind, parts in stacks.items():
-            g = plan.groups[kind]
-            ((sh, stack),) = parts
-            with torch.cuda.device(sh.device):
-                if isinstance(stack, RowTable):  # device uploads: the one-launch gather into the stack
-                    buf = self.packer.device_bucket(("in", kind, sh.index), (n, g.stride), TORCH_DTYPE[g.store_dtype],
-                                                    sh.device)
-                    stack.gather_into(buf)
-                    stack = buf
-            dense[kind] = (sh, stack)
-        sh, stack = dense[KIND_F32]
-        with torch.cuda.device(sh.device):
-            row = self._center_row(g32, centre, sh.device)
-            runs = key_runs(g32)
-            grams = self.packer.device_bucket(("gram", KIND_F32), (len(runs), n, n), torch.float64, sh.device)
-            work = self.packer.device_bucket(("gram_work", KIND_F32), (max(gram_workspace(n, c1 - c0) for c0, c1 in runs),),
-                                             torch.uint8, sh.device)
-            for i, (c0, c1) in enumerate(runs):
-                gram_stack(stack, center=row, n_clients=n, col_begin=c0, n_cols=c1 - c0, out=grams[i], workspace=work)
-            host = grams.cpu().numpy()  # the one synchronisation of the round before its result
-        gram = host[0].copy()
-        for part in host[1:]:  # partial Grams add: in key order, float64
-            gram += part
-        # (a slab, the caller's memory read in place, needs no hold for the Gram launches: the copy
-        # above has waited for them; the selected rows' reduce keeps it through its row table)
-        selected, scores = krum.krum_select(gram, f, m)
-        self.last_krum = {"gram": gram, "scores": scores, "selected": selected, "centered": row is not None}
-        sel = [int(i) for i in selected]
-        # The mean of the selected uploads, planned as ensemble([1] * m, ..., the round's keys) plans
-        # it.  Over the ROUND's keys in the round's order, never the selected uploads' own: the
-        # stack is laid out by the round's plan (upload 0's key order, the keys common to all N),
-        # and a left-out upload must not move a column by ordering its dict differently or by
-        # lacking a key.
-        plan_m = make_plan([1] * m, [w_local_lst[i] for i in sel], list(plan.keys))
-        sums = {}
-        for kind, (dsh, st) in dense.items():
-            gm, g = plan_m.groups.get(kind), plan.groups[kind]
-            if gm is None or gm.stride != g.stride or [(s.key, s.offset, s.numel) for s in gm.segments] != [
-                    (s.key, s.offset, s.numel) for s in g.segments]:
-                raise RuntimeError(f"the selected uploads' {kind} bucket is not laid out as the round's")
-            segs = [s for s in gm.segments if s.numel > 0]
-            esz = st.element_size()
-            ptrs = np.empty((len(segs), m), dtype=np.int64)
-            base = np.array([st.data_ptr() + i * st.stride(0) * esz for i in sel], dtype=np.int64)
-            for j, s in enumerate(segs):
-                ptrs[j] = base + s.offset * esz
-            with torch.cuda.device(dsh.device):
-                table = RowTable(self.packer, plan_m, gm, segs, ptrs, [st], None, dsh.device)
-                if kind == KIND_F32:
-                    # rows of a 16-B aligned stack at 64-element offsets: fa_reduce_f32_rows reads them in place
-                    if not table.aligned:
-                        raise RuntimeError("the fp32 stack's rows are not 16-B aligned")
-                    total = table
-                else:
-                    total = self.packer.device_bucket(("sel", kind), (m, gm.stride), TORCH_DTYPE[gm.store_dtype], dsh.device)
-                    table.gather_into(total)
-            sums[kind] = [(dsh, total)]
-        if set(plan_m.groups) != set(dense):
-            raise RuntimeError("the selected uploads' buckets are not the round's")
-        self.last_plan = plan_m
-        try:
-            results = self._server_step(plan_m, sums, server_opt)
-        finally:
-            for kind, ((dsh, total),) in sums.items():
-                if isinstance(total, RowTable):
-                    total.release()  # the stack (a slab: the caller's memory) stays alive until the reduce is done
-        return self._finish(plan_m, results)
-
-    @staticmethod
-    def _check_center(g32: Group, center):
-        """[(segment, flat tensor)] of `center`'s fp32 keys, or None; ValueError for a centre that is
-        no dict, lacks a key of the bucket or has another element count.  Touches no device."""
-        if center is None:
-            return None
-        if not hasattr(center, "keys"):
-            raise ValueError("center must be a w_glob-like dict or None")
-        out = []
-        for s in g32.segments:
-            if s.numel == 0:
-                continue
-            if s.key not in center:
-                raise ValueError(f"center has no key {s.key!r}")
-            v = center[s.key]
-            v = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-            if v.numel() != s.numel:
-                raise ValueError(f"center[{s.key!r}] has {v.numel()} elements, the uploads have {s.numel}")
-            out.append((s, v.reshape(-1)))
-        return out
-
-    def _center_row(self, g32: Group, centre, device):
-        """_check_center's pieces laid out as one fp32 row of the bucket (zeros elsewhere), or None."""
-        if centre is None:
-            return None
-        row = self.packer.device_bucket(("center", KIND_F32), (g32.stride,), torch.float32, device)
-        row.zero_()
-        for s, v in centre:
-            row[s.offset : s.offset + s.numel].copy_(v, non_blocking=False)
-        return row
 
     # -- the server step of a round: one-launch and streamed rounds alike ------------------------
     def _server_step(self, plan: BucketPlan, sums: dict, server_opt) -> dict:
@@ -480,21 +277,6 @@ class Aggregator:
         if self.output == "device":
             return assemble_on_device(plan, results, self.device)
         return self.packer.unpack(plan, results, as_torch=plan.input_kind == "torch")
-
-
-def key_runs(g: Group) -> list:
-    """The column ranges [c0, c1) of a bucket that hold keys and nothing else: consecutive keys with
-    no padding between them form one run.  What a Gram is taken over: a stack's padding columns are
-    never written by a pack and may hold another layout's values."""
-    runs = []
-    for s in g.segments:
-        if s.numel == 0:
-            continue
-        if runs and runs[-1][1] == s.offset:
-            runs[-1][1] = s.offset + s.numel
-        else:
-            runs.append([s.offset, s.offset + s.numel])
-    return [tuple(r) for r in runs]
 
 
 def assemble_on_device(plan: BucketPlan, results: dict, device) -> dict:

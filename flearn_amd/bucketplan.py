@@ -94,6 +94,21 @@ class Group:
         return row_layout(((s.key, s.shape, s.offset) for s in self.segments), self.stride)
 
 
+def key_runs(g: Group) -> list:
+    """The column ranges [c0, c1) of a bucket that hold keys and nothing else: consecutive keys with
+    no padding between them form one run.  What a Gram is taken over: a stack's padding columns are
+    never written by a pack and may hold another layout's values."""
+    runs = []
+    for s in g.segments:
+        if s.numel == 0:
+            continue
+        if runs and runs[-1][1] == s.offset:
+            runs[-1][1] = s.offset + s.numel
+        else:
+            runs.append([s.offset, s.offset + s.numel])
+    return [tuple(r) for r in runs]
+
+
 @dataclass
 class BucketPlan:
     keys: list  # output key order

@@ -208,6 +208,25 @@ class Packer:
         ev.record(torch.cuda.current_stream(device))
         self._held.append((ev, objs))
 
+    def hold_slab(self, kind: str, stacks, device) -> None:
+        """`hold` the stacks of `kind` when its last pack was a slab: the caller's memory, read in
+        place by the launches queued so far, stays alive until they have read it."""
+        if self.last_row_tables.get(kind) == "slab":
+            self.hold(list(stacks), device)
+
+    def dense_stack(self, plan: BucketPlan, kind: str, parts, n: int) -> tuple:
+        """(shard, [n, stride] device tensor) of what `pack` returned for one unsharded bucket: a
+        RowTable (device uploads) is gathered, in one launch, into the bucket's input stack; a
+        stack comes back as packed."""
+        ((sh, stack),) = parts
+        if isinstance(stack, RowTable):
+            g = plan.groups[kind]
+            with torch.cuda.device(sh.device):
+                buf = self.device_bucket(("in", kind, sh.index), (n, g.stride), TORCH_DTYPE[g.store_dtype], sh.device)
+                stack.gather_into(buf)
+            stack = buf
+        return sh, stack
+
     def device_bucket(self, tag, shape, dtype, device=None):
         """A reusable device buffer (contents undefined)."""
         dev = self.device if device is None else torch.device(device)

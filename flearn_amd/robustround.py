@@ -1,0 +1,239 @@
+"""The robust rounds of the engine, bound on Aggregator as `ensemble_trimmed` and `ensemble_krum`.
+
+Both need every client at once, on one device, with unit weights: they share their refusals
+(`_refuse`, `_plan_unit_weights`), pack the uploads as ever, take each bucket as one dense
+[N, stride] stack (Packer.dense_stack) and end in the server step every round ends in
+(Aggregator._server_step).  The trimmed round makes each bucket's sums with ops.trim_sum_stack; the
+Krum round is three steps: `client_gram` (ops.gram_stack per run of keys, to the host),
+krum.krum_select, and `selected_sums` (the selected rows, read where they are).
+"""
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+import torch
+
+from . import _native as na
+from . import krum, ops
+from .bucketplan import TORCH_DTYPE, BucketPlan, Group, key_runs, make_plan
+from .rowtable import RowTable
+from .semantics import KIND_F16, KIND_F32
+from .serverstate import DynState, ServerOptimizer
+
+
+def _refuse(agg, server_opt) -> None:
+    """What no robust round does, refused before the uploads are looked at."""
+    if agg.chunk_clients is not None:
+        raise ValueError("a robust round needs every client at once: chunk_clients is not supported")
+    if agg._dist:
+        raise ValueError("a robust round is not sharded over a process group (group=)")
+    if len(agg.devices) > 1:
+        raise ValueError("a robust round runs on one device: devices=[...] with several devices is not supported")
+    if isinstance(server_opt, DynState):
+        raise TypeError("FedDyn's h update needs the plain sum over all clients: no robust round with Dyn state")
+
+
+def _plan_unit_weights(w_local_lst, key_lst, max_clients: int, what: str) -> BucketPlan:
+    """make_plan's plan for Python-int weights of 1 (key intersection, layouts and errors as in
+    `ensemble`), for at most max_clients uploads and no float16 bucket."""
+    n = len(w_local_lst)
+    if n > max_clients:
+        raise ValueError(f"a {what} round takes at most {max_clients} clients, got {n}")
+    plan = make_plan([1] * n, w_local_lst, key_lst)
+    if KIND_F16 in plan.groups:
+        raise TypeError("float16 uploads: a robust round aggregates fp32 / float64 / int64 buckets only")
+    return plan
+
+
+# -- coordinate-wise trimmed mean and median ---------------------------------------------------
+def ensemble_trimmed(agg, w_local_lst, trim: int, key_lst=None, server_opt: ServerOptimizer | None = None):
+    """The coordinate-wise trimmed mean of the uploads (Yin et al., ICML 2018): per element, the
+    N clients' values in IEEE totalOrder, the `trim` smallest and the `trim` largest dropped, the
+    rest summed in ascending order in the bucket's sum type and divided by N - 2 * trim (the
+    median is trim = (N - 1) // 2).  There are no weights: a client cannot buy influence with
+    its own agg_weight, and the result does not depend on the order of the uploads.  The plan is
+    make_plan's for Python-int weights (key intersection, layouts and errors as in `ensemble`),
+    the uploads are packed as ever (host, device, slab), fa_trim_sum makes each bucket's sums,
+    and the server step — the divide, a fused AVGM / OPT update, the three output modes — is
+    the one a streamed round ends in.
+
+    Refused before anything is queued: float16 buckets and FedDyn state (TypeError: its h
+    update needs the plain sum over all N); several devices, group= and chunk_clients
+    (ValueError: every client must be present for a column's order statistics); more than
+    128 clients and a trim outside 0 <= 2 * trim < N (ValueError)."""
+    _refuse(agg, server_opt)
+    plan = _plan_unit_weights(w_local_lst, key_lst, na.TRIM_MAX_CLIENTS, "robust")
+    n = plan.n_clients
+    if isinstance(trim, bool) or not isinstance(trim, (int, np.integer)) or trim < 0 or 2 * trim >= n:
+        raise ValueError(f"trim must be an integer with 0 <= 2 * trim < {n} clients, got {trim!r}")
+    trim = int(trim)
+    # the divide is by the kept count (the plan is make_plan's cached one: a copy carries it)
+    groups = {kind: Group(kind, dataclasses.replace(g.numerics, denom=float(n - 2 * trim)), g.segments, g.stride)
+              for kind, g in plan.groups.items()}
+    plan = dataclasses.replace(plan, groups=groups)
+    agg.last_plan = plan
+    packer = agg.packer
+    stacks = packer.pack(plan, w_local_lst)
+    sums = {}
+    for kind, parts in stacks.items():
+        g = plan.groups[kind]
+        sh, stack = packer.dense_stack(plan, kind, parts, n)
+        with torch.cuda.device(sh.device):
+            ak = ops.acc_kind_of(kind, g.numerics.mode)
+            acc = packer.device_bucket(("acc", kind), (g.stride,), ops._ACC_TORCH[ak], sh.device)
+            ops.trim_sum_stack(ak, stack, trim, acc, n_clients=n)
+            packer.hold_slab(kind, [stack], sh.device)
+        sums[kind] = [(sh, ops.FoldedSum(acc, ak, n, sh.width))]
+    return agg._finish(plan, agg._server_step(plan, sums, server_opt))
+
+
+# -- Krum / multi-Krum ---------------------------------------------------------------------------
+def ensemble_krum(agg, w_local_lst, f: int, m: int, key_lst=None, server_opt: ServerOptimizer | None = None,
+                  center=None):
+    """Multi-Krum (Blanchard et al., NeurIPS 2017; Krum is m = 1): the m uploads closest to their
+    N - f - 2 nearest neighbours are averaged, the others are left out whole, and `last_krum`
+    says which.  The uploads are planned (make_plan for Python-int weights) and packed as ever
+    (host, device, slab); the fp32 bucket's client Gram matrix (ops.gram_stack, centred on
+    `center`) goes to the host (8 N^2 bytes per run of keys), krum.krum_select picks the uploads,
+    and their mean is taken from the device stacks already there — the fp32 bucket through a
+    row table of the selected rows' addresses, the 8-byte buckets gathered into a compact stack
+    — with unit weights, in upload order: bit-identical to
+    ensemble([1] * m, [the selected uploads in upload order], the round's keys, server_opt) — the keys
+    common to all N uploads (or key_lst), in the round's order, whoever is selected.
+
+    Distances are measured on the fp32 bucket only: float64 / int64 values (BN counters and the
+    like) do not enter them, and are averaged over the selected clients like the rest.
+    center: a w_glob-like dict (the server's own state, never a client's upload); its fp32 keys
+    are laid out into one fp32 row and subtracted from every upload before the products, which
+    keeps the cancellation in G_ii + G_jj - 2 G_ij harmless for models that differ little.
+
+    self.last_krum = {"gram", "scores", "selected", "centered"} (host arrays) is the audit.
+    Refused before anything is queued: float16 buckets and FedDyn state (TypeError); several
+    devices, group=, chunk_clients, more than 128 clients, bad f / m, and uploads without an
+    fp32 bucket to measure distances on (ValueError).  More than f non-finite uploads: ValueError
+    after the Gram."""
+    _refuse(agg, server_opt)
+    plan = _plan_unit_weights(w_local_lst, key_lst, na.GRAM_MAX_CLIENTS, "Krum")
+    n = plan.n_clients
+    f, m = krum.check_counts(n, f, m)
+    g32 = plan.groups.get(KIND_F32)
+    if g32 is None or not any(s.numel > 0 for s in g32.segments):
+        raise ValueError("Krum measures distances on the fp32 bucket, and these uploads have none")
+    centre = _check_center(g32, center)  # refused here, before anything is queued
+    agg.last_plan = plan
+    agg.last_krum = None
+    stacks = agg.packer.pack(plan, w_local_lst)
+    dense = {kind: agg.packer.dense_stack(plan, kind, parts, n) for kind, parts in stacks.items()}
+    gram = client_gram(agg, plan, dense, centre)
+    # (a slab, the caller's memory read in place, needs no hold for the Gram launches: client_gram's
+    # copy to the host has waited for them; the selected rows' reduce keeps it through its row table)
+    selected, scores = krum.krum_select(gram, f, m)
+    agg.last_krum = {"gram": gram, "scores": scores, "selected": selected, "centered": centre is not None}
+    sel = [int(i) for i in selected]
+    # The mean of the selected uploads, planned as ensemble([1] * m, ..., the round's keys) plans
+    # it.  Over the ROUND's keys in the round's order, never the selected uploads' own: the
+    # stack is laid out by the round's plan (upload 0's key order, the keys common to all N),
+    # and a left-out upload must not move a column by ordering its dict differently or by
+    # lacking a key.
+    plan_m = make_plan([1] * m, [w_local_lst[i] for i in sel], list(plan.keys))
+    sums = selected_sums(agg, plan, plan_m, dense, sel)
+    agg.last_plan = plan_m
+    try:
+        results = agg._server_step(plan_m, sums, server_opt)
+    finally:
+        for ((_, total),) in sums.values():
+            if isinstance(total, RowTable):
+                total.release()  # the stack (a slab: the caller's memory) stays alive until the reduce is done
+    return agg._finish(plan_m, results)
+
+
+def client_gram(agg, plan: BucketPlan, dense: dict, centre):
+    """The clients' float64 [N, N] Gram matrix of the fp32 bucket, on the host: one ops.gram_stack
+    launch per run of keys, `centre` (_check_center's pieces, or None) subtracted from every row,
+    and the one synchronisation of the round before its result."""
+    g32, n = plan.groups[KIND_F32], plan.n_clients
+    sh, stack = dense[KIND_F32]
+    with torch.cuda.device(sh.device):
+        row = _center_row(agg, g32, centre, sh.device)
+        runs = key_runs(g32)
+        grams = agg.packer.device_bucket(("gram", KIND_F32), (len(runs), n, n), torch.float64, sh.device)
+        work_bytes = max(ops.gram_workspace(n, c1 - c0) for c0, c1 in runs)
+        work = agg.packer.device_bucket(("gram_work", KIND_F32), (work_bytes,), torch.uint8, sh.device)
+        for i, (c0, c1) in enumerate(runs):
+            ops.gram_stack(stack, center=row, n_clients=n, col_begin=c0, n_cols=c1 - c0, out=grams[i], workspace=work)
+        host = grams.cpu().numpy()
+    gram = host[0].copy()
+    for part in host[1:]:  # partial Grams add: in key order, float64
+        gram += part
+    return gram
+
+
+def same_layout(gm: Group | None, g: Group) -> bool:
+    """The selected uploads' bucket has the round's stride and its keys at the round's columns."""
+    return gm is not None and gm.stride == g.stride and [(s.key, s.offset, s.numel) for s in gm.segments] == [
+        (s.key, s.offset, s.numel) for s in g.segments]
+
+
+def selected_sums(agg, plan: BucketPlan, plan_m: BucketPlan, dense: dict, sel: list) -> dict:
+    """kind -> [(shard, the rows `sel` of the round's dense stack)] for the server step over plan_m:
+    the fp32 bucket as a RowTable of the rows' addresses, read in place (the caller releases it),
+    the 8-byte buckets gathered into a compact [m, stride] stack."""
+    m = len(sel)
+    sums = {}
+    for kind, (dsh, st) in dense.items():
+        gm = plan_m.groups.get(kind)
+        if not same_layout(gm, plan.groups[kind]):
+            raise RuntimeError(f"the selected uploads' {kind} bucket is not laid out as the round's")
+        segs = [s for s in gm.segments if s.numel > 0]
+        esz = st.element_size()
+        ptrs = np.empty((len(segs), m), dtype=np.int64)
+        base = np.array([st.data_ptr() + i * st.stride(0) * esz for i in sel], dtype=np.int64)
+        for j, s in enumerate(segs):
+            ptrs[j] = base + s.offset * esz
+        with torch.cuda.device(dsh.device):
+            table = RowTable(agg.packer, plan_m, gm, segs, ptrs, [st], None, dsh.device)
+            if kind == KIND_F32:
+                # rows of a 16-B aligned stack at 64-element offsets: fa_reduce_f32_rows reads them in place
+                if not table.aligned:
+                    raise RuntimeError("the fp32 stack's rows are not 16-B aligned")
+                total = table
+            else:
+                total = agg.packer.device_bucket(("sel", kind), (m, gm.stride), TORCH_DTYPE[gm.store_dtype], dsh.device)
+                table.gather_into(total)
+        sums[kind] = [(dsh, total)]
+    if set(plan_m.groups) != set(dense):
+        raise RuntimeError("the selected uploads' buckets are not the round's")
+    return sums
+
+
+def _check_center(g32: Group, center):
+    """[(segment, flat tensor)] of `center`'s fp32 keys, or None; ValueError for a centre that is
+    no dict, lacks a key of the bucket or has another element count.  Touches no device."""
+    if center is None:
+        return None
+    if not hasattr(center, "keys"):
+        raise ValueError("center must be a w_glob-like dict or None")
+    out = []
+    for s in g32.segments:
+        if s.numel == 0:
+            continue
+        if s.key not in center:
+            raise ValueError(f"center has no key {s.key!r}")
+        v = center[s.key]
+        v = v.detach() if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+        if v.numel() != s.numel:
+            raise ValueError(f"center[{s.key!r}] has {v.numel()} elements, the uploads have {s.numel}")
+        out.append((s, v.reshape(-1)))
+    return out
+
+
+def _center_row(agg, g32: Group, centre, device):
+    """_check_center's pieces laid out as one fp32 row of the bucket (zeros elsewhere), or None."""
+    if centre is None:
+        return None
+    row = agg.packer.device_bucket(("center", KIND_F32), (g32.stride,), torch.float32, device)
+    row.zero_()
+    for s, v in centre:
+        row[s.offset : s.offset + s.numel].copy_(v, non_blocking=False)
+    return row

@@ -20,7 +20,22 @@ import torch
 from .avg import AVG
 
 
-class TrimmedMean(AVG):
+class _RobustRound(AVG):
+    """What the robust strategies share: FedAVG's client side, every client at once, and an optional
+    ServerOptimizer (`server_opt`, set by the subclass) fused into the round's divide."""
+
+    server_opt = None
+
+    def server(self, ensemble_params_lst, round_):
+        """{"w_glob": the robust round's result (server_ensemble: the trimmed mean, or the mean of the
+        selected uploads)}; client-data errors -> server_exception, device errors propagate."""
+        return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, server_opt=self.server_opt)}
+
+    def begin_round(self, round_):
+        raise ValueError("a robust round needs every client at once: begin_round() is not supported")
+
+
+class TrimmedMean(_RobustRound):
     """Coordinate-wise trimmed mean.  trim: a float in [0, 0.5) is the fraction dropped per side,
     t = floor(trim * N) each round; an int is the count per side (0 <= 2 t < N is checked per
     round).  trim = 0 is a mean summed in sorted order, not FedAVG's list-order sum.
@@ -60,13 +75,6 @@ class TrimmedMean(AVG):
         presence by server_pre_processing and not used."""
         return self.engine.ensemble_trimmed(w_local_lst, self.trim_count(len(w_local_lst)), key_lst, server_opt=server_opt)
 
-    def server(self, ensemble_params_lst, round_):
-        """{"w_glob": trimmed mean}; client-data errors -> server_exception, device errors propagate."""
-        return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, server_opt=self.server_opt)}
-
-    def begin_round(self, round_):
-        raise ValueError("a robust round needs every client at once: begin_round() is not supported")
-
 
 class Median(TrimmedMean):
     """Coordinate-wise median: the trimmed mean with t = (N - 1) // 2, which keeps one value for
@@ -80,7 +88,7 @@ class Median(TrimmedMean):
         return max(0, (n_clients - 1) // 2)
 
 
-class MultiKrum(AVG):
+class MultiKrum(_RobustRound):
     """Multi-Krum (Blanchard et al., NeurIPS 2017): with up to f bad uploads among N, an upload's
     score is the sum of its squared distances to its N - f - 2 nearest other uploads; the m uploads
     of lowest score are averaged with equal weights and the others are left out whole.  The engine's
@@ -128,14 +136,6 @@ class MultiKrum(AVG):
             self._prev_glob = {k: v.detach().clone() if isinstance(v, torch.Tensor) else np.array(v)
                                for k, v in w_glob.items()}
         return w_glob
-
-    def server(self, ensemble_params_lst, round_):
-        """{"w_glob": mean of the selected uploads}; client-data errors -> server_exception, device
-        errors propagate."""
-        return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, server_opt=self.server_opt)}
-
-    def begin_round(self, round_):
-        raise ValueError("a robust round needs every client at once: begin_round() is not supported")
 
 
 class Krum(MultiKrum):

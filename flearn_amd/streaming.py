@@ -19,7 +19,6 @@ import torch
 from .bucketplan import TORCH_DTYPE, BucketPlan, Group, _as_array_meta, make_plan
 from .ops import _ACC_TORCH, FoldedSum, acc_kind_of, fold_finish, fold_stack  # noqa: F401 (re-exported)
 from .packer import Packer
-from .rowtable import RowTable
 from .semantics import _is_weight, resolve
 
 _F16, _F64 = np.dtype(np.float16), np.dtype(np.float64)
@@ -157,18 +156,12 @@ class RoundAccumulator:
         with torch.cuda.device(dev):
             for kind, parts in stacks.items():
                 g = plan.groups[kind]
-                ((sh, stack),) = parts
-                if isinstance(stack, RowTable):  # device uploads: the one-launch gather into the chunk stack
-                    buf = packer.device_bucket(("in", kind, sh.index), (len(ps), g.stride), TORCH_DTYPE[g.store_dtype],
-                                               sh.device)
-                    stack.gather_into(buf)
-                    stack = buf
+                _, stack = packer.dense_stack(plan, kind, parts, len(ps))  # the chunk stack
                 ak = acc_kind_of(kind, g.numerics.mode)
                 acc = agg.packer.device_bucket(("acc", kind), (g.stride,), _ACC_TORCH[ak], dev)
                 fold_stack(ak, stack, agg._weights(g.numerics, dev), self._acc.get(kind), acc, n_clients=len(ps))
                 self._acc[kind] = acc
-                if packer.last_row_tables.get(kind) == "slab":  # the caller's memory, read in place
-                    packer.hold([stack], dev)
+                packer.hold_slab(kind, [stack], dev)
         self._chunks += 1
 
     # -- the end of the round -----------------------------------------------------------------

@@ -4,7 +4,9 @@ one-launch and streamed rounds share: every name the two modules defined is stil
 them and is the object of its new home; the modules import each other in one direction, at module
 level; the shared step asks a stack-like and a folded-like sum for the same thing and advances
 the state only after the sum's launch returned; and ops.FoldedSum hands fa_fold_finish the
-epilogue reduce_stack would build.  No GPU."""
+epilogue reduce_stack would build.  The robust rounds live in robustround and are bound on the
+class; what they share with the other rounds (Packer.dense_stack, Packer.hold_slab,
+bucketplan.key_runs) is checked here on CPU stand-ins.  No GPU."""
 import ast
 import contextlib
 import importlib
@@ -33,7 +35,7 @@ KEPT = ["_F64", "_ONE_W32", "OUTPUTS", "Aggregator", "assemble_on_device"]
 STREAMING_MOVED = ["_ACC_TORCH", "acc_kind_of", "fold_stack", "fold_finish"]
 STREAMING_KEPT = ["_F16", "_F64", "RoundAccumulator"]
 
-ENGINE = ("ops", "serverstate", "smallround", "aggregator", "streaming", "dist")
+ENGINE = ("ops", "serverstate", "smallround", "robustround", "aggregator", "streaming", "dist")
 ROOT = Path(__file__).resolve().parent.parent / "flearn_amd"
 
 
@@ -65,6 +67,21 @@ def test_small_round_switches_stay_on_the_class():
     assert Aggregator._small_round is smallround._small_round  # bound as a method: no call layer in between
 
 
+def test_robust_rounds_are_bound_on_the_class():
+    from flearn_amd import aggregator, bucketplan, robustround
+    from flearn_amd.aggregator import Aggregator
+
+    assert aggregator.key_runs is bucketplan.key_runs
+    assert Aggregator.ensemble_trimmed is robustround.ensemble_trimmed  # bound as _small_round is
+    assert Aggregator.ensemble_krum is robustround.ensemble_krum
+    assert Aggregator._check_center is robustround._check_center  # a staticmethod: no engine needed
+    assert Aggregator._center_row is robustround._center_row
+    assert Aggregator._check_center(None, None) is None
+    assert Aggregator.last_krum is None  # before the first Krum round
+    for name in ("ensemble_trimmed", "ensemble_krum", "_check_center", "_center_row"):
+        assert getattr(Aggregator, name).__doc__, name
+
+
 def _package_imports(mod: str):
     """(names of the package a module's imports mention, those of them below module level)."""
     tree = ast.parse((ROOT / f"{mod}.py").read_text())
@@ -88,8 +105,92 @@ def test_import_graph_has_one_direction():
     for mod in ("serverstate", "smallround"):
         assert not _package_imports(mod)[0] & {"aggregator", "streaming"}, mod
     assert "aggregator" not in _package_imports("streaming")[0]
+    assert not _package_imports("robustround")[0] & {"aggregator", "streaming"}
     for mod in ENGINE:  # no import of one another inside a function
         assert not _package_imports(mod)[1] & set(ENGINE), mod
+
+
+# -- what the rounds share of the packer and the plan ---------------------------------------------
+
+
+def _pool_packer(last_row_tables=()):
+    """A Packer with no device: its buffers come from the CPU and `hold` only records."""
+    from flearn_amd.packer import Packer
+
+    class PoolPacker(Packer):
+        def __init__(self):
+            self.made, self.held, self.last_row_tables = {}, [], dict(last_row_tables)
+
+        def device_bucket(self, tag, shape, dtype, device=None):
+            assert tag not in self.made, tag
+            self.made[tag] = torch.zeros(shape, dtype=dtype)
+            return self.made[tag]
+
+        def hold(self, objs, device):
+            self.held.append((objs, device))
+
+    return PoolPacker()
+
+
+def _fake_row_table(log):
+    from flearn_amd.rowtable import RowTable
+
+    class FakeRows(RowTable):
+        def gather_into(self, stack):
+            log.append(stack)
+
+    return object.__new__(FakeRows)
+
+
+def test_dense_stack_gathers_a_row_table_once_and_passes_a_stack_through(monkeypatch):
+    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())  # CPU shards
+    _, plan, (sh, other) = _two_cpu_shards()
+    stride = plan.f32.stride
+    packer = _pool_packer()
+    stack = torch.zeros(2, stride)
+    got = packer.dense_stack(plan, KIND_F32, [(sh, stack)], 2)
+    assert got[0] is sh and got[1] is stack and not packer.made  # as packed: no buffer, no copy
+    log = []
+    got = packer.dense_stack(plan, KIND_F32, [(other, _fake_row_table(log))], 5)
+    ((tag, buf),) = packer.made.items()
+    assert tag == ("in", KIND_F32, other.index) and buf.shape == (5, stride) and buf.dtype == torch.float32
+    assert got[0] is other and got[1] is buf
+    assert len(log) == 1 and log[0] is buf  # one gather, into that bucket
+    with pytest.raises(ValueError):  # a column-sharded bucket has no dense stack
+        packer.dense_stack(plan, KIND_F32, [(sh, stack), (other, stack)], 2)
+    with pytest.raises(ValueError):
+        packer.dense_stack(plan, KIND_F32, [], 2)
+
+
+def test_hold_slab_holds_only_what_was_read_in_place():
+    a, b = torch.zeros(3), torch.zeros(3)
+    packer = _pool_packer({KIND_F32: "slab"})
+    packer.hold_slab(KIND_F32, (t for t in (a, b)), "dev")  # any iterable of stacks
+    ((objs, device),) = packer.held
+    assert len(objs) == 2 and objs[0] is a and objs[1] is b and device == "dev"
+    for how in ("rows", "gather", "copy"):
+        packer = _pool_packer({KIND_F32: how})
+        packer.hold_slab(KIND_F32, [a], "dev")
+        assert packer.held == [], how
+    packer = _pool_packer({KIND_F32: "slab"})
+    packer.hold_slab("f64", [a], "dev")  # a kind the last pack did not see as device uploads
+    assert packer.held == []
+
+
+def test_key_runs_merge_adjacent_keys_and_split_at_padding():
+    from flearn_amd.bucketplan import Group, Segment, key_runs
+
+    f32 = np.dtype(np.float32)
+
+    def group(*segs):  # (numel, offset) per key
+        return Group(KIND_F32, None, [Segment(f"k{i}", (n,), n, off, f32) for i, (n, off) in enumerate(segs)], 512)
+
+    assert key_runs(group((64, 0), (128, 64), (5, 192))) == [(0, 197)]  # whole ALIGN spans: no gap
+    assert key_runs(group((10, 0), (64, 64), (3, 128), (7, 192))) == [(0, 10), (64, 131), (192, 199)]
+    # a zero-element key takes a padded span of its own and is no run; nor does it join its neighbours
+    assert key_runs(group((64, 0), (0, 64), (64, 128))) == [(0, 64), (128, 192)]
+    assert key_runs(group((0, 0), (64, 64), (0, 128))) == [(64, 128)]
+    assert key_runs(group((0, 0))) == [] and key_runs(group()) == []
 
 
 # -- the shared f32 step ------------------------------------------------------------------------

@@ -84,7 +84,7 @@ def test_median_of_the_bn_model_counts_through_the_elem_kernel(output, bnmodel, 
         real(*a, **k)
         launched.append(ops.last_launch()[0])
 
-    monkeypatch.setattr("flearn_amd.aggregator.trim_sum_stack", spy)
+    monkeypatch.setattr(ops, "trim_sum_stack", spy)
     got = Median(output=output).server(upload(bnmodel, 3), 0)["w_glob"]
     want = rr.ensemble(bnmodel, 1)
     check(got, want, output, f"bn median {output}", {k: np.asarray(v).dtype for k, v in bnmodel[0].items()})

@@ -238,10 +238,12 @@ inline int64_t window_width(int64_t ncols, int count) {
 // deep, at most 16 (~64 KiB of client rows in flight per block).  Wider windows are swept piece
 // after piece (column-major), D = 1.  vmax follows the sums' registers per oct: 4 VGPRs (f16 sums)
 // 16, 8 (fp32 sums) 8, 16 (f64 sums) 4.  A window of at most one chunk per block runs as
-// single-wave blocks, 16 rows deep.
-inline Plan plan_f16_window(int vmax, int64_t ncols, int cus) {
+// single-wave blocks, 16 rows deep.  forced: fa_set_reduce_grid (0 = the geometry chooses); V, W
+// and D follow from the share on that grid by the same rule, and a share past the widest piece is
+// swept in rounds as on the natural grid.
+inline Plan plan_f16_window(int vmax, int64_t ncols, int cus, int forced = 0) {
   const int64_t chunks = row_chunks(ncols, 8);
-  const int64_t grid = one_piece_grid(chunks, cus, 0);
+  const int64_t grid = one_piece_grid(chunks, cus, forced);
   const int64_t share = ceil_div(chunks, grid);  // chunks per block
   const int w = share <= 1 ? 1 : 4;
   int v = 1;

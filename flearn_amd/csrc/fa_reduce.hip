@@ -146,7 +146,7 @@ int launch_balanced(const Window<P, double>& a, hipStream_t s) {
 template <class HP, int DIV, int VMAX>
 int launch_reduce_h16(const uint16_t* stack, int64_t stride, int n, const void* w, int64_t col0, int64_t ncols,
                       const EpiH16& e, hipStream_t s) {
-  const Plan p = plan_f16_window(VMAX, ncols, device_cus());
+  const Plan p = plan_f16_window(VMAX, ncols, device_cus(), g_reduce_grid.load(std::memory_order_relaxed));
   const typename HP::w_t* wt = static_cast<const typename HP::w_t*>(w);
 #define FA_ROWS_H16(V, DEPTH, W)                                                                               \
   case V * 100 + W:                                                                                            \

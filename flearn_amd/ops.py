@@ -424,7 +424,8 @@ def apply_dyn(glob, h, theta, n_clients: int, alpha: float = 0.01, *, out32=None
 
 
 def set_reduce_grid(grid: int) -> int:
-    """Blocks of the fp32 stack reduce, process-wide (fa_set_reduce_grid): 0 = the library's
+    """Blocks of the stack reduces (fp32 and float16), the folds, the trimmed sums and the Gram
+    matrix, process-wide (fa_set_reduce_grid): 0 = the library's
     choice; fewer leave CUs to kernels running beside the reduce (RCCL's gather in the multi-GPU
     pipeline).  Returns the previous setting.  Results never depend on it."""
     L = na.load()

@@ -168,7 +168,10 @@ int fa_reduce_i64(const int64_t* stack, int64_t row_stride, int32_t n_clients,
  *   out16   : [n_cols] half bits: the float16 result for _NP16, else fl16(fl32(result)) — what
  *             load_state_dict of the result into a half module stores.  Sums that leave the half
  *             range are +-inf, subnormals are kept.  Any of the three may be NULL (not all);
- *             out16 / out32 16-byte, out64 32-byte aligned.                                     */
+ *             out16 / out32 16-byte, out64 32-byte aligned.
+ * fa_set_reduce_grid applies (the piece width follows the share of a block on the forced grid;
+ * the results do not depend on it); fa_last_launch names the instantiation, e.g.
+ * "reduce_kernel_rows_h16<AccH16Pk,0,16,1,4,true>".                                             */
 int fa_reduce_f16(const void* stack, int64_t row_stride, int32_t n_clients, int32_t mode,
                   const void* weights, double denom, int64_t col_begin, int64_t n_cols,
                   void* out16, float* out32, double* out64, void* stream);
@@ -252,7 +255,8 @@ int fa_gather_rows_f64(double* stack, int64_t row_stride, int32_t n_clients, con
 int fa_fill_uniform_f32(float* dst, int64_t row_stride, int32_t n_rows, int64_t n_cols,
                         uint64_t seed, int64_t row_begin, int64_t col_global_begin, void* stream);
 
-/* Process-wide grid of the fp32 stack reduce (fa_reduce_f32 / _splitn's fallback): the number
+/* Process-wide grid of the stack reduces (fa_reduce_f32 / _splitn's fallback, fa_reduce_f16, and
+ * the entries below that say "fa_set_reduce_grid applies"): the number
  * of blocks the row-pipelined kernels are launched with.  0 (the default) = the library's own
  * choice (~0.75 blocks per CU, one block per CU at most: DESIGN.md section 4).  A smaller grid
  * leaves CUs free for kernels that run beside the reduce — RCCL's all-gather of the previous

@@ -1,7 +1,7 @@
 // geometry_probe.cpp — the reduce geometry's decisions on a CPU box (tests/test_geometry_plan.py).
 // One query per line on stdin, one answer line each:
 //   f32 mode op n ncols cus forced splitn -> family V W D KG EPIB wide16 grid
-//   f16 vmax ncols cus                    -> family V W D KG EPIB wide16 grid
+//   f16 vmax ncols cus [forced]           -> family V W D KG EPIB wide16 grid   (no forced: 0)
 //   win op ncols                          -> window count and width
 //   bal chunks slots                      -> grid
 #include "fa_geometry.hpp"
@@ -24,8 +24,8 @@ int main() {
     if (!std::strcmp(kind, "f32") &&
         std::sscanf(line, "%*s %d %d %d %lld %d %d %d", &mode, &op, &n, &a, &cus, &forced, &splitn) == 7) {
       show(fa::plan_f32_window(mode, op, n, a, cus, forced, splitn != 0));
-    } else if (!std::strcmp(kind, "f16") && std::sscanf(line, "%*s %d %lld %d", &mode, &a, &cus) == 3) {
-      show(fa::plan_f16_window(mode, a, cus));
+    } else if (!std::strcmp(kind, "f16") && std::sscanf(line, "%*s %d %lld %d %d", &mode, &a, &cus, &forced) >= 3) {
+      show(fa::plan_f16_window(mode, a, cus, forced));
     } else if (!std::strcmp(kind, "win") && std::sscanf(line, "%*s %d %lld", &op, &a) == 2) {
       const int count = fa::window_count(op, a);
       std::printf("%d %lld\n", count, (long long)fa::window_width(a, count));

@@ -97,6 +97,48 @@ def test_float16_geometry(probe):
         assert (p["V"], p["W"], p["D"], p["grid"]) == _HALF[vmax][share], (vmax, share)
 
 
+def test_every_float16_case_plans_its_target(probe):
+    """The H16 cases of tests/instantiation_cases.py on their forced grid of 3: the share table of
+    that module (1, 3, 7, 13, 27, 61, 130 chunks per block), VMAX by the mode."""
+    cases = ic.H16_CASES
+    got = [_plan(f) for f in probe([f"f16 {ic.H16_MODES[c.mode][2]} {c.n_cols} {CUS} {c.grid}" for c in cases])]
+    for c, p in zip(cases, got):
+        assert p["family"] == "rows_h16"
+        assert ic.h16_name(c.mode, p["V"], p["D"], p["W"]) == c.target, c
+        assert p["grid"] == min(c.grid, ic.h16_chunks(c.n_cols)) == (2 if c.share == 1 else 3), c
+        assert -(-ic.h16_chunks(c.n_cols) // p["grid"]) == c.share
+    assert len({c.target for c in cases}) == ic.FAMILY_COUNTS["rows_h16"] == 27
+
+
+def test_float16_forced_grid_points(probe):
+    """A forced grid changes the grid alone: V, W and D are those the same share has on the natural
+    grid (_HALF above), and a forced 0 is the three-field query."""
+    for vmax in _HALF:
+        for share, (v, w, d, _) in _HALF[vmax].items():
+            for forced in (1, 3, 7):
+                p = _plan(probe([f"f16 {vmax} {share * forced * 512} {CUS} {forced}"])[0])
+                assert (p["V"], p["W"], p["D"], p["grid"]) == (v, w, d, forced), (vmax, share, forced)
+    pairs = [(f"f16 {vmax} {ncols} {cus}", f"f16 {vmax} {ncols} {cus} 0") for vmax in (16, 8, 4) for cus in (256, 304, 64)
+             for ncols in (1, 513, 98_304, 6_400_003, 12_600_000)]
+    for a, b in pairs:
+        assert probe([a]) == probe([b]), a
+    # a forced grid wider than the window: one block per chunk
+    assert _plan(probe([f"f16 16 1025 {CUS} 160"])[0])["grid"] == 3
+
+
+def test_float16_plan_restatement(probe):
+    """ic.plan_f16, which the GPU tests name their expected launches with, is the header's rule:
+    on the natural and on forced grids, for three CU counts."""
+    points = [(vmax, ncols, cus, forced) for vmax in (16, 8, 4) for cus in (256, 304, 64) for forced in (0, 1, 2, 3, 5, 500)
+              for ncols in (1, 7, 512, 513, 520, 1025, 8192, ic.h16_chunk_cols(27), ic.h16_chunk_cols(70), 98_305,
+                            cus * 3 * 128 + 1, cus * 3 * 512 * 4 - 1029, cus * 3 * 512 * 16 - 1029, cus * 3 * 512 * 32 - 1029,
+                            cus * 64 * 512 - 5, cus * 64 * 512 + 5)]
+    got = probe([f"f16 {vmax} {ncols} {cus} {forced}" for vmax, ncols, cus, forced in points])
+    for pt, f in zip(points, got):
+        p = _plan(f)
+        assert (p["V"], p["D"], p["W"], p["grid"]) == ic.plan_f16(*pt), pt
+
+
 def test_window_split(probe):
     mi = 1 << 20
     want = {  # (op, columns): (windows, columns per window)

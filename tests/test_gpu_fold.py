@@ -4,7 +4,11 @@ The expected value is always oracle.c_reduce(mode, the WHOLE stack, the WHOLE we
 the reference's arithmetic on the undivided list (strategy.py:123-129) — so chunking must be
 invisible: results are bit-identical, NaN exactly where the oracle has NaN.  Epilogues are
 oracle.c_update / c_update_dyn on that mean, as tests/test_gpu_epilogue_values.py checks the fused
-families.  Every output and accumulator is followed by 96 sentinel elements that must survive."""
+families.  Every output and accumulator is followed by 96 sentinel elements that must survive.
+Every launch's full name comes from the table of tests/instantiation_cases.py, which
+tests/test_kernel_inventory.py holds equal to the built library: the fold kernel of the kind, and
+the one fold_finish_kernel<A,T,OP> of the (kind, mode, op) — all 19 are reached here (mean and the
+five epilogues in the three fp32 modes, the mean of the two 8-byte kinds)."""
 import ctypes
 import re
 
@@ -16,6 +20,7 @@ import oracle
 from epilogue_table import HYPERS, first_diffs, same_values, stack_for, table
 from flearn_amd import _native as na
 from flearn_amd import aggregator as agg
+from instantiation_cases import FOLD_ELEM, FOLD_ROWS_POLICY, FOLD_TARGETS, FOLD_V, fold_finish_name, fold_rows_name
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +89,7 @@ def fold_chain(cuda, kind, x, w, splits, col_begin, ncols, *, double=False):
     L = na.lib()
     sdt, wdt, adt = KINDS[kind]
     accs = [Arr(ncols, adt, cuda), Arr(ncols, adt, cuda) if double else None]
+    shipped = {fold_rows_name(kind, v) for v in FOLD_V} if kind in FOLD_ROWS_POLICY else {FOLD_ELEM[kind]}
     cur, i0, names = None, 0, []
     for j, k in enumerate(splits):
         out = accs[j % 2] if double else accs[0]
@@ -93,7 +99,7 @@ def fold_chain(cuda, kind, x, w, splits, col_begin, ncols, *, double=False):
         kernel, grid, launches = agg.last_launch()
         assert (kernel is None) == (ncols == 0)
         if kernel is not None:
-            assert kernel.startswith("fold_kernel_") and launches == 1 and grid >= 1, kernel
+            assert kernel in shipped and launches == 1 and grid >= 1, kernel
             names.append(kernel)
         cur, i0 = out, i0 + k
     assert i0 == x.shape[0]
@@ -109,7 +115,8 @@ def finish(cuda, kind, mode, acc, denom, ncols, *, epi=None, want32=True, want64
     na.check(rc, "fa_fold_finish")
     kernel, _, launches = agg.last_launch()
     if ncols:
-        assert kernel.startswith("fold_finish_kernel<") and launches == 1, kernel
+        op = epi.op if epi is not None else na.OP_MEAN
+        assert kernel == fold_finish_name(kind, mode, op) and launches == 1, kernel
     return out32, out64
 
 
@@ -229,7 +236,7 @@ def test_chunkings_at_every_pipeline_depth(share, kind, mode, omode, cuda, grid)
     for s in chunkings(n, d):
         b, names = run_round(cuda, kind, mode, omode, xh, wh, denom, s)
         v, dd = DEPTH_SHARES[share]
-        assert set(names) == {f"fold_kernel_rows<{'AccF32' if kind == na.ACC_F32 else 'AccF32W64'},{v},{dd},4,true>"}
+        assert dd == 64 // (4 * v) and set(names) == {fold_rows_name(kind, v)}
         bits.add(b)
     assert len(bits) == 1
 
@@ -393,6 +400,16 @@ def test_epilogue_table_through_fold_and_finish(op, kind, mode, omode, state, cu
     for name, a in (("out32", out32), ("out64", out64), ("l32", l32), ("v", v), ("v_out", v_out), ("acc", acc)):
         assert a is None or a.tail_intact(), f"{name}: written past the end"
     assert np.isnan(want).any() and not np.isnan(want).all()
+
+
+def test_the_parametrisations_reach_every_finish_instantiation():
+    """finish() holds every launch to fold_finish_name(kind, mode, op); the (kind, mode, op) of
+    test_every_chunking_of_n_gives_the_single_sum (plain mean) and of
+    test_epilogue_table_through_fold_and_finish (ops 1-5) are all 19 shipped instantiations."""
+    means = {fold_finish_name(kind, mode, na.OP_MEAN) for kind, mode, _ in FP32_MODES + WIDE_MODES}
+    fused = {fold_finish_name(kind, mode, op) for kind, mode, _ in FP32_MODES for op in range(1, 6)}
+    assert means | fused == {t for t in FOLD_TARGETS if t.startswith("fold_finish_kernel<")}
+    assert len(means | fused) == 19
 
 
 # ---------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ import torch
 
 import gram_ref as gr
 from flearn_amd import ops
+from instantiation_cases import gram_name
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +70,7 @@ def test_exact_integers_every_depth(n, cuda, cus):
         got, name, grid = run(x, cuda, centre)
         assert np.array_equal(got, int_gram(x, centre)), (n, centre is not None)
         p = gr.launch_plan(n, 1000, cus)
-        assert name == f"gram_kernel_tile<{p.np_},{'true' if centre is not None else 'false'},true>"
+        assert name == gram_name(p.np_, centre is not None)
         assert grid == p.grid and p.np_ >= n
 
 

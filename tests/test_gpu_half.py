@@ -4,7 +4,11 @@ Oracle: tests/half_ref.py, the numpy restatement that tests/test_half_host.py pi
 captured from the reference (tests/golden/half_*.npz).  Rule: finite values and infinities bit for
 bit, NaNs by position — for out64, out32 and out16 alike.  Shapes: the 16-B unit (8 halves), the
 1-KiB wave chunk (512), one piece +- 1 column, every piece width the geometry chooses, more pieces
-than blocks; client counts around the pipeline depth D of the kernel each width runs."""
+than blocks; client counts around the pipeline depth D of the kernel each width runs.  Where a test
+claims the shape it reaches, fa_last_launch must name it: the expected instantiation comes from
+plan_f16_window's rule (instantiation_cases.plan_f16, held to the header by
+tests/test_geometry_plan.py) on the device's CU count.  tests/test_gpu_half_instantiations.py
+reaches every instantiation at small widths on a forced grid."""
 import numpy as np
 import pytest
 import torch
@@ -15,6 +19,7 @@ from flearn_amd import _native as na
 from flearn_amd import aggregator as agg
 from flearn_amd import semantics
 from golden_io import Golden, cases
+from instantiation_cases import h16_name, h16_plan_name
 
 pytestmark = pytest.mark.gpu
 
@@ -86,6 +91,7 @@ def check(cuda, mode_name, x, col_begin=0, n_cols=None, outs=("out64", "out32", 
     n_cols = stride - col_begin if n_cols is None else n_cols
     num = weights_for(mode_name, n)
     got = run_kernel(cuda, MODES[mode_name], x, num, col_begin, n_cols, outs)
+    launch = agg.last_launch()
     q = half_ref.reduce_rows(MODES[mode_name], np.ascontiguousarray(x[:, col_begin : col_begin + n_cols]), num.weights,
                              num.denom)
     assert q.dtype == num.out_dtype
@@ -95,6 +101,7 @@ def check(cuda, mode_name, x, col_begin=0, n_cols=None, outs=("out64", "out32", 
         tail = got[k][n_cols:]
         fill = np.int16(0x1234).view(np.float16) if k == "out16" else -7.0
         assert (tail == fill).all(), (mode_name, k, "stored past the window")
+    return launch
 
 
 def round_up(v, m):
@@ -110,14 +117,17 @@ def cus(cuda):
 @pytest.mark.parametrize("p", [1, 7, 8, 9, 511, 512, 513, 1023, 1024, 1025])
 def test_widths(cuda, mode_name, p):
     """The 16-B unit, the 1-KiB chunk = one single-wave piece, +- 1 column, two pieces."""
-    check(cuda, mode_name, make_stack(3, round_up(p, 8), seed=p))
+    launch = check(cuda, mode_name, make_stack(3, round_up(p, 8), seed=p))
+    chunks = -(-p // 512)  # at most 3: one single-wave block per chunk on any device
+    assert launch == (h16_name(MODES[mode_name], 1, 16, 1), chunks, 1)
 
 
 @pytest.mark.parametrize("mode_name", list(MODES))
 @pytest.mark.parametrize("n", [1, 2, 16, 17, 31, 32, 33, 100])
 def test_depths_single_wave_pieces(cuda, mode_name, n):
     """N around D = 16, the depth of the one-chunk-per-block kernel a 513-column window runs."""
-    check(cuda, mode_name, make_stack(n, 520, seed=n))
+    launch = check(cuda, mode_name, make_stack(n, 520, seed=n))
+    assert launch == (h16_name(MODES[mode_name], 1, 16, 1), 2, 1)
 
 
 @pytest.mark.parametrize("mode_name", list(MODES))
@@ -125,7 +135,9 @@ def test_more_pieces_than_three_quarters_of_the_cus(cuda, cus, mode_name):
     """A grid's worth of one-chunk pieces + 1 column: the first window on 4-wave blocks (V = 1)."""
     grid = int(cus * 0.75 + 0.5)
     p = grid * 512 + 1
-    check(cuda, mode_name, make_stack(17, round_up(p, 8), seed=3))
+    launch = check(cuda, mode_name, make_stack(17, round_up(p, 8), seed=3))
+    assert launch == (h16_name(MODES[mode_name], 1, 16, 4), grid, 1)
+    assert launch[:2] == h16_plan_name(MODES[mode_name], round_up(p, 8), cus)
 
 
 @pytest.mark.parametrize("mode_name", list(MODES))
@@ -136,9 +148,15 @@ def test_every_piece_width(cuda, cus, mode_name, v):
     N = 2D + 1 and N = 1.  Modes with wider sums stop at their widest piece and sweep more pieces."""
     grid = int(cus * 0.75 + 0.5)
     p = grid * 4 * v * 512 - 1029  # a ragged, odd end inside the last block's piece
-    d = max(1, 16 // min(v, VMAX[mode_name]))
+    vk = min(v, VMAX[mode_name])  # the piece the kernel runs: v KiB per wave, at most the mode's widest
+    d = max(1, 16 // vk)
+    want = h16_plan_name(MODES[mode_name], round_up(p, 8), cus)
+    assert want[0] == h16_name(MODES[mode_name], vk, d, 4), want  # what the docstring claims, on this CU count
+    assert (-(-round_up(p, 8) // 512) > want[1] * 4 * vk) == (v > vk)  # several pieces per block
     for n in (2 * d + 1, 1):
-        check(cuda, mode_name, make_stack(n, round_up(p, 8), seed=v), outs=("out64", "out16") if v < 32 else ("out16",))
+        launch = check(cuda, mode_name, make_stack(n, round_up(p, 8), seed=v),
+                       outs=("out64", "out16") if v < 32 else ("out16",))
+        assert launch == want + (1,)
 
 
 @pytest.mark.parametrize("mode_name", list(MODES))

@@ -9,6 +9,7 @@ import torch
 import robust_ref as rr
 from flearn_amd import _native as na
 from flearn_amd import ops
+from instantiation_cases import TRIM_ELEM, trim_rows_name
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +57,7 @@ def test_depths_both_sides_of_every_np(n, cuda):
         got = run(x, t, cuda)
         assert rr.same_bits(got, rr.trimmed_sum(x, t)), (n, t)
         name, grid, launches = ops.last_launch()
-        assert name == f"trim_kernel_rows<{expected_np(n)},4,true>" and grid == 2 and launches == 1
+        assert name == trim_rows_name(expected_np(n)) and grid == 2 and launches == 1
 
 
 def test_trims_cover_the_issue_axis():
@@ -91,7 +92,7 @@ def test_several_pieces_per_block(cuda):
         name, grid, _ = ops.last_launch()
     finally:
         ops.set_reduce_grid(prev)
-    assert grid == 3 and name == "trim_kernel_rows<16,4,true>"  # 17 pieces on 3 blocks
+    assert grid == 3 and name == trim_rows_name(16)  # 17 pieces on 3 blocks
     assert rr.same_bits(got, rr.trimmed_sum(x[:, :4099], 2))
     assert rr.same_bits(run(x, 2, cuda, n_cols=4099), got) and ops.last_launch()[1] == 17
 
@@ -145,10 +146,10 @@ def test_float64_and_int64_sums(n, cuda):
     for t in trims(n):
         got = run(x64, t, cuda, kind=na.ACC_F64, n_cols=70)
         assert rr.same_bits(got, rr.trimmed_sum(x64[:, :70], t)), ("f64", n, t)
-        assert ops.last_launch()[0] == "trim_kernel_elem<double>"
+        assert ops.last_launch() == (TRIM_ELEM[na.ACC_F64], 1, 1)
         got = run(xi, t, cuda, kind=na.ACC_I64, n_cols=70)
         assert rr.same_bits(got, rr.trimmed_sum(xi[:, :70], t)), ("i64", n, t)
-        assert ops.last_launch()[0].startswith("trim_kernel_elem<") and ops.last_launch()[1] == 1
+        assert ops.last_launch() == (TRIM_ELEM[na.ACC_I64], 1, 1)
     if n == 10:
         assert (np.abs(xi[:, 10:].astype(np.float64)).sum(0) > 2.0**63).any()  # the int64 sums did wrap
 
@@ -157,7 +158,7 @@ def test_float64_and_int64_sums(n, cuda):
 def test_instantiation_named_by_last_launch(n, np_, cuda):
     x = data(n, 64, n)
     run(x, 0, cuda)
-    assert ops.last_launch() == (f"trim_kernel_rows<{np_},4,true>", 1, 1)
+    assert ops.last_launch() == (trim_rows_name(np_), 1, 1)
 
 
 def test_finish_gives_the_trimmed_mean(cuda):

@@ -9,8 +9,8 @@ Drop-in use with an unchanged flearn server:
 The hot path (Strategy.server -> server_ensemble) runs hand-written HIP kernels for gfx950
 through the C ABI in include/flearn_amd.h; there is no CPU fallback.
 """
-from .strategy import (AVG, AVGM, BN, LG, LG_R, OPT, SGD, BaseEncrypt, Distill, Dyn, Krum, Median, MultiKrum, ParentStrategy,
-                       Prox, Strategy, TrimmedMean)
+from .strategy import (AVG, AVGM, BN, LG, LG_R, OPT, SGD, BaseEncrypt, Distill, Dyn, Krum, Median, MultiKrum, NormClip,
+                       ParentStrategy, Prox, Strategy, TrimmedMean)
 from .strategy import convert_to_np, convert_to_tensor
 from .utils import base_strategy_lst, setup_seed, setup_strategy
 from .wire import Encrypt
@@ -33,6 +33,7 @@ __all__ = [
     "Median",
     "Krum",
     "MultiKrum",
+    "NormClip",
     "Strategy",
     "ParentStrategy",
     "BaseEncrypt",

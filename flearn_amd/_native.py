@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 19
+ABI_VERSION = 20
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -32,6 +32,7 @@ PREC_F32, PREC_F64 = 0, 1
 ACC_F32, ACC_F32_W64, ACC_F64, ACC_I64 = 0, 1, 2, 3  # fa_fold accumulator kinds (FA_ACC_*)
 TRIM_MAX_CLIENTS = 128  # fa_trim_sum's deepest client stack (FA_TRIM_MAX_CLIENTS)
 GRAM_MAX_CLIENTS = 128  # fa_gram_f32's (FA_GRAM_MAX_CLIENTS)
+CLIP_MAX_CLIENTS = 128  # fa_rownorm2_f32's and fa_clip_sum_f32's (FA_CLIP_MAX_CLIENTS)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
 #: every symbol include/flearn_amd.h declares (checked by tests/test_cabi.py)
@@ -70,6 +71,9 @@ EXPORTS = (
     "fa_trim_sum",
     "fa_gram_workspace",
     "fa_gram_f32",
+    "fa_rownorm_workspace",
+    "fa_rownorm2_f32",
+    "fa_clip_sum_f32",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -244,6 +248,9 @@ def load(require_gpu: bool = False):
                 "fa_trim_sum": ([I32, P, I64, I32, I32, P, I64, I64, P], ctypes.c_int),
                 "fa_gram_workspace": ([I32, I64], I64),
                 "fa_gram_f32": ([P, I64, I32, P, I64, I64, P, I64, P, P], ctypes.c_int),
+                "fa_rownorm_workspace": ([I32, I64], I64),
+                "fa_rownorm2_f32": ([P, I64, I32, P, I64, I64, P, I64, P, P], ctypes.c_int),
+                "fa_clip_sum_f32": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

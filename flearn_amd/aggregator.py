@@ -6,7 +6,8 @@ HBM, run ONE fused reduce launch per bucket kind on torch's current stream, and 
 fresh dict with the reference's value types.  `begin_round` aggregates the same round in chunks of
 clients (streaming.py); both end in the same server step (`Aggregator._server_step`), fed by
 either kind of weighted sum (ops.StackSum, ops.FoldedSum).  The robust rounds, `ensemble_trimmed`
-(coordinate-wise trimmed mean and median) and `ensemble_krum` (Krum / multi-Krum), are
+(coordinate-wise trimmed mean and median), `ensemble_krum` (Krum / multi-Krum) and
+`ensemble_clipped` (norm clipping), are
 robustround.py's, bound on the class; they end in the same server step.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
@@ -72,9 +73,11 @@ class Aggregator:
     #: the robust rounds (robustround.py), bound the same way; last_krum: the last Krum round's audit
     ensemble_trimmed = robustround.ensemble_trimmed
     ensemble_krum = robustround.ensemble_krum
+    ensemble_clipped = robustround.ensemble_clipped
     _check_center = staticmethod(robustround._check_center)
     _center_row = robustround._center_row
     last_krum = None
+    last_clip = None  # the last clipped round's audit
 
     def __init__(self, device=None, output: str = "reference", workers: int = 8, devices=None, group=None,
                  reorder: bool = False, chunk_clients: int | None = None):

@@ -1,5 +1,5 @@
 // fa_geometry.hpp — which kernel instantiation runs for a shape, and on what grid: the reduces, the
-// folds, the trimmed sums and the Gram matrix.
+// folds, the trimmed sums, the Gram matrix and the norm-clipped rounds.
 //
 // Plain C++17, pure integer decisions: no HIP, no globals, no device queries.  fa_reduce.hip asks
 // these functions for a Plan and turns it into a launch; tests/geometry_probe.cpp asks them on a
@@ -375,6 +375,61 @@ inline GramPlan plan_gram_window(int n_clients, int64_t n_cols, int cus, int for
   const int64_t share = ceil_div(chunks, grid) * kc;
   return GramPlan{np, kc, kGramLc, chunks, grid, share, kGramLc + ceil_div(share, kGramLc),
                   grid * (int64_t)(np ? np : kGramTile) * (np ? np : kGramTile) * 4};
+}
+
+// Norm-clipped rounds (fa_rownorm2_f32 / fa_clip_sum_f32).  Both kernels sweep
+// the window as fold_kernel_rows does: kFoldW waves, the narrowest piece (V KiB per wave) that covers
+// the block's share, D = 64/(V*W) rows in flight.  The clip sum takes plan_fold_window(FA_ACC_F32)
+// as it is.  The norms take the same sizing on at most kRownormGridCap blocks (one fp32 partial per
+// client and block in the workspace), and the plan, not the kernel, cuts the pieces: `pc` 1-KiB
+// chunks per piece, block b sweeping pieces b, b + grid, ..., never more blocks than pieces.
+// chain: the longest sequence of fp32 roundings behind one client's partial — V fused multiply-adds
+// per element slot of a lane's quads and 2 adds joining the 4 slots, kRownormWaveAdds adds of the
+// wave's fixed tree (4 DPP steps inside a row of 16 lanes, then the 4 rows in order), one add per
+// piece of the block into the wave's running sum, and W - 1 adds of the waves' sums at the block's
+// end.  All terms are squares, so |d2 - d2_ref| <= (gamma(chain) + grid * 2^-52) * d2_ref.
+constexpr int kClipMaxClients = FA_CLIP_MAX_CLIENTS;
+constexpr int kRownormGridCap = 512;
+constexpr int kRownormWaveAdds = 7;
+
+struct RownormPlan {
+  int V, W, D;      // quads per lane and piece (0: n_clients out of range), waves, rows in flight
+  int64_t chunks;   // 1-KiB chunks of the window
+  int64_t pc;       // chunks per piece (<= W * V)
+  int64_t pieces;
+  int64_t grid;     // blocks = partial rows in the workspace
+  int64_t per_block;  // the most pieces one block sweeps
+  int64_t chain;
+  int64_t workspace_bytes;  // grid * n_clients * 4
+};
+
+inline RownormPlan plan_rownorm_window(int n_clients, int64_t n_cols, int cus, int forced_grid) {
+  const bool ok = n_clients >= 1 && n_clients <= kClipMaxClients;
+  const int64_t chunks = row_chunks(n_cols < 1 ? 1 : n_cols);
+  int64_t grid = forced_grid > 0 ? forced_grid : natural_grid(cus);
+  if (forced_grid <= 0 && chunks > grid * kPieceChunks && chunks <= rows_grid_max(cus) * kPieceChunks)
+    grid = ceil_div(chunks, kPieceChunks);
+  if (grid > kRownormGridCap) grid = kRownormGridCap;
+  if (grid > chunks) grid = chunks;
+  if (grid < 1) grid = 1;
+  const int64_t share = ceil_div(chunks, grid);
+  int v = 1;
+  while (v < kPieceChunks / kFoldW && share > v * kFoldW) v *= 2;
+  const int64_t k = ceil_div(chunks, grid * kFoldW * v);  // rounds
+  const int64_t pc = ceil_div(chunks, grid * k);
+  const int64_t pieces = ceil_div(chunks, pc);
+  if (grid > pieces) grid = pieces;
+  const int64_t per_block = ceil_div(pieces, grid);
+  return RownormPlan{ok ? v : 0, kFoldW, kPieceChunks / (v * kFoldW), chunks, pc, pieces, grid, per_block,
+                     v + 2 + kRownormWaveAdds + per_block + kFoldW - 1, grid * (ok ? n_clients : 0) * 4};
+}
+
+// What fa_rownorm_workspace returns: enough for any device and any forced grid (a launch has at most
+// min(kRownormGridCap, chunks) blocks)
+inline int64_t rownorm_workspace_bytes(int n_clients, int64_t n_cols) {
+  int64_t blocks = n_cols > (int64_t)kRownormGridCap * 256 ? kRownormGridCap : row_chunks(n_cols < 1 ? 1 : n_cols);
+  if (blocks > kRownormGridCap) blocks = kRownormGridCap;
+  return blocks * n_clients * 4;
 }
 
 // The sorting network of trim_kernel_rows: Batcher's odd-even merge sort on NP = 2^q slots, as

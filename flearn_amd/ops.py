@@ -3,7 +3,9 @@ engine (aggregator.py, streaming.py, serverstate.py) call.
 
 `reduce_stack*` sum, divide and update a client stack in one launch; `fold_stack` adds a chunk of
 clients to a typed accumulator and `fold_finish` divides and updates a finished one; `trim_sum_stack`
-makes the accumulator of a robust round (per column, the sorted clients' middle values).  `StackSum`
+makes the accumulator of a robust round (per column, the sorted clients' middle values), `gram_stack`
+the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
+accumulator of a norm-clipped round.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
 """
@@ -338,6 +340,88 @@ def gram_stack(stack: torch.Tensor, *, center: torch.Tensor | None = None, n_cli
     return out.reshape(-1)[: n * n].view(n, n)
 
 
+def rownorm_workspace(n_clients: int, n_cols: int) -> int:
+    """Bytes of workspace rownorm2_stack needs for this shape (fa_rownorm_workspace): enough on any
+    device and under any set_reduce_grid."""
+    need = na.load().fa_rownorm_workspace(int(n_clients), int(n_cols))
+    if need < 0:
+        na.check(int(need), "fa_rownorm_workspace")
+    return int(need)
+
+
+def _check_f32_stack(stack, col_begin, n_cols, n_clients, max_clients):
+    if not isinstance(stack, torch.Tensor) or stack.dim() != 2 or stack.stride(1) != 1 or not stack.is_cuda:
+        raise ValueError("stack must be a 2-D device tensor with contiguous rows")
+    if stack.dtype != torch.float32:
+        raise TypeError(f"stack must be torch.float32, got {stack.dtype}")
+    n, ncols = _check_window(stack.shape, col_begin, n_cols, n_clients)
+    if n > max_clients:
+        raise ValueError(f"at most {max_clients} clients, got {n}")
+    return n, ncols
+
+
+def _check_center_row(center, stack, need):
+    if (not isinstance(center, torch.Tensor) or center.dtype != torch.float32 or center.device != stack.device
+            or center.dim() != 1 or not center.is_contiguous() or center.numel() < need):
+        raise ValueError(f"center must be a contiguous 1-D torch.float32 tensor of at least {need} "
+                         "elements on the stack's device")
+
+
+def rownorm2_stack(stack: torch.Tensor, *, center: torch.Tensor | None = None, n_clients: int | None = None,
+                   col_begin: int = 0, n_cols: int | None = None, out: torch.Tensor | None = None,
+                   workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """The clients' squared update norms over the window [col_begin, +n_cols) of an fp32 stack
+    (fa_rownorm2_f32), queued on torch's current stream: out[i] = sum_k fl32(x_i[k] - center[k])^2, a
+    float64 [N] device tensor, summed in a fixed order (the same bits for the same inputs, device and
+    grid).  center: an fp32 device row laid out like a stack row (at least col_begin + n_cols long),
+    or None.  At most na.CLIP_MAX_CLIENTS clients.  out: a contiguous float64 tensor of at least N
+    elements to write (else a fresh one); workspace: a 16-B aligned device buffer of at least
+    rownorm_workspace(N, n_cols) bytes (else a fresh one)."""
+    n, ncols = _check_f32_stack(stack, col_begin, n_cols, n_clients, na.CLIP_MAX_CLIENTS)
+    if ncols < 1:
+        raise ValueError("the column window is empty")
+    if center is not None:
+        _check_center_row(center, stack, col_begin + ncols)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float64, device=stack.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != stack.device
+          or not out.is_contiguous() or out.numel() < n):
+        raise ValueError(f"out must be a contiguous torch.float64 tensor of at least {n} elements on the stack's device")
+    need = rownorm_workspace(n, ncols)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=stack.device)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != stack.device or not workspace.is_contiguous()
+          or workspace.numel() * workspace.element_size() < need):
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on the stack's device")
+    rc = na.lib().fa_rownorm2_f32(stack.data_ptr(), stack.stride(0), n, _ptr(center), col_begin, ncols,
+                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(), out.data_ptr(),
+                                  na.stream_handle(stack.device))
+    na.check(rc, "fa_rownorm2_f32")
+    return out.reshape(-1)[:n]
+
+
+def clip_sum_stack(stack: torch.Tensor, center: torch.Tensor, scale: torch.Tensor, acc_out: torch.Tensor, *,
+                   n_clients: int | None = None, col_begin: int = 0, n_cols: int | None = None) -> None:
+    """acc_out[c] = the running fp32 sum, in list order, of the clients' clipped uploads of column
+    col_begin + c (fa_clip_sum_f32), queued on torch's current stream: row i as it is for
+    scale[i] >= 1, fl32(g + fl32(scale[i] * fl32(x - g))) for 0 < scale[i] < 1, and the centre g, the
+    row unread, otherwise.  center: an fp32 device row laid out like a stack row; scale: fp32 [N] on
+    the device.  The accumulator is na.ACC_F32's: fold_finish divides it.  At most
+    na.CLIP_MAX_CLIENTS clients."""
+    n, ncols = _check_f32_stack(stack, col_begin, n_cols, n_clients, na.CLIP_MAX_CLIENTS)
+    _check_center_row(center, stack, col_begin + ncols)
+    if (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.device != stack.device
+            or not scale.is_contiguous() or scale.numel() < n):
+        raise ValueError(f"scale must be a contiguous torch.float32 tensor of at least {n} elements on the stack's device")
+    if (not isinstance(acc_out, torch.Tensor) or acc_out.dtype != torch.float32 or not acc_out.is_cuda
+            or acc_out.numel() < ncols or not acc_out.is_contiguous() or acc_out.device != stack.device):
+        raise ValueError(f"acc_out must be a contiguous torch.float32 tensor of at least {ncols} elements on the "
+                         "stack's device")
+    rc = na.lib().fa_clip_sum_f32(stack.data_ptr(), stack.stride(0), n, center.data_ptr(), scale.data_ptr(),
+                                  acc_out.data_ptr(), col_begin, ncols, na.stream_handle(stack.device))
+    na.check(rc, "fa_clip_sum_f32")
+
+
 # ---------------------------------------------------------------------------------------------
 # a round's weighted sum, either way: what the engine's server step divides and updates
 # ---------------------------------------------------------------------------------------------
@@ -424,8 +508,8 @@ def apply_dyn(glob, h, theta, n_clients: int, alpha: float = 0.01, *, out32=None
 
 
 def set_reduce_grid(grid: int) -> int:
-    """Blocks of the stack reduces (fp32 and float16), the folds, the trimmed sums and the Gram
-    matrix, process-wide (fa_set_reduce_grid): 0 = the library's
+    """Blocks of the stack reduces (fp32 and float16), the folds, the trimmed sums, the Gram
+    matrix, the update norms and the clipped sum, process-wide (fa_set_reduce_grid): 0 = the library's
     choice; fewer leave CUs to kernels running beside the reduce (RCCL's gather in the multi-GPU
     pipeline).  Returns the previous setting.  Results never depend on it."""
     L = na.load()

@@ -1,11 +1,14 @@
-"""The robust rounds of the engine, bound on Aggregator as `ensemble_trimmed` and `ensemble_krum`.
+"""The robust rounds of the engine, bound on Aggregator as `ensemble_trimmed`, `ensemble_krum` and
+`ensemble_clipped`.
 
-Both need every client at once, on one device, with unit weights: they share their refusals
+All need every client at once, on one device, with unit weights: they share their refusals
 (`_refuse`, `_plan_unit_weights`), pack the uploads as ever, take each bucket as one dense
 [N, stride] stack (Packer.dense_stack) and end in the server step every round ends in
 (Aggregator._server_step).  The trimmed round makes each bucket's sums with ops.trim_sum_stack; the
 Krum round is three steps: `client_gram` (ops.gram_stack per run of keys, to the host),
-krum.krum_select, and `selected_sums` (the selected rows, read where they are).
+krum.krum_select, and `selected_sums` (the selected rows, read where they are).  The clipped round
+measures each client's update norm (`client_norm2`: ops.rownorm2_stack per run of keys, to the host),
+takes its radius and scales from clip.py and sums the clipped uploads with ops.clip_sum_stack.
 """
 from __future__ import annotations
 
@@ -15,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _native as na
-from . import krum, ops
+from . import clip, krum, ops
 from .bucketplan import TORCH_DTYPE, BucketPlan, Group, key_runs, make_plan
 from .rowtable import RowTable
 from .semantics import KIND_F16, KIND_F32
@@ -146,6 +149,93 @@ def ensemble_krum(agg, w_local_lst, f: int, m: int, key_lst=None, server_opt: Se
             if isinstance(total, RowTable):
                 total.release()  # the stack (a slab: the caller's memory) stays alive until the reduce is done
     return agg._finish(plan_m, results)
+
+
+# -- norm clipping ------------------------------------------------------------------------------
+def ensemble_clipped(agg, w_local_lst, tau, quantile, key_lst=None, server_opt: ServerOptimizer | None = None,
+                     center=None):
+    """The mean of the uploads after each client's update x_i - g has been projected onto the ball of
+    radius tau around `center` (g, the server's own model): norm clipping (Sun et al. 2019; the clipping
+    step of McMahan et al. 2018).  Exactly one of tau (a float > 0) and quantile (q in (0, 1]: tau is
+    the ceil(q * F)-th smallest of the F finite client norms, Andrew et al. 2021) is given.  No upload
+    is left out and no bound on the number of attackers is needed: a scaled upload keeps its direction
+    and loses its leverage, and a NaN / inf upload becomes a zero update (the centre), so the global
+    model stays finite however many uploads are bad.
+
+    The uploads are planned (make_plan for Python-int weights) and packed as ever (host, device,
+    slab).  Only the fp32 bucket is measured and clipped: d2_i = sum_k fl32(x_ik - g_k)^2 per run of
+    keys (ops.rownorm2_stack), one copy to the host — the round's one synchronisation —, the radius
+    and the scales in float64 there (clip.py), then one ops.clip_sum_stack over the bucket: row i as
+    it is where s_i = 1, fl32(g + fl32(s_i * fl32(x - g))) where 0 < s_i < 1, g (the row unread)
+    where s_i = 0, summed in list order in fp32 and divided by N in the one server step.  With every
+    s_i = 1 the round is bit-identical to ensemble([1] * N, uploads, keys, server_opt).  Float64 /
+    int64 buckets (BN counters) do not enter the norm and are averaged over all N clients.
+    center=None: no clip, the round is that unit-weight mean itself.
+
+    self.last_clip = {"norm2", "scale", "tau", "clipped", "replaced", "centered"} (host arrays; clipped:
+    the indices with s < 1, replaced: those with s = 0) is the audit.  Refused before anything is
+    queued: float16 buckets and FedDyn state (TypeError); several devices, group=, chunk_clients, more
+    than 128 clients, a bad tau / quantile, uploads without an fp32 bucket and a centre lacking a key
+    (ValueError).  No finite norm under a quantile radius: ValueError after the norms."""
+    _refuse(agg, server_opt)
+    plan = _plan_unit_weights(w_local_lst, key_lst, na.CLIP_MAX_CLIENTS, "clipped")
+    n = plan.n_clients
+    clip.check_radius(tau, quantile)
+    g32 = plan.groups.get(KIND_F32)
+    if g32 is None or not any(s.numel > 0 for s in g32.segments):
+        raise ValueError("norm clipping measures the fp32 bucket, and these uploads have none")
+    centre = _check_center(g32, center)  # refused here, before anything is queued
+    agg.last_clip = None
+    if centre is None:
+        w_glob = agg.ensemble([1] * n, w_local_lst, key_lst, server_opt)
+        none = np.empty(0, dtype=np.int64)
+        agg.last_clip = {"norm2": None, "scale": None, "tau": None, "clipped": none, "replaced": none.copy(),
+                         "centered": False}
+        return w_glob
+    agg.last_plan = plan
+    packer = agg.packer
+    stacks = packer.pack(plan, w_local_lst)
+    dense = {kind: packer.dense_stack(plan, kind, parts, n) for kind, parts in stacks.items()}
+    sh, stack = dense[KIND_F32]
+    with torch.cuda.device(sh.device):
+        row = _center_row(agg, g32, centre, sh.device)
+        norm2 = client_norm2(agg, g32, stack, row, n, sh.device)
+        radius = clip.clip_radius(norm2, tau, quantile)
+        scale = clip.clip_scales(norm2, radius)
+        agg.last_clip = {"norm2": norm2, "scale": scale, "tau": radius, "clipped": np.flatnonzero(scale < 1.0),
+                         "replaced": np.flatnonzero(scale == 0.0), "centered": True}
+        dscale = packer.device_bucket(("clip_scale", KIND_F32), (n,), torch.float32, sh.device)
+        dscale.copy_(torch.from_numpy(scale))
+        acc = packer.device_bucket(("acc", KIND_F32), (g32.stride,), torch.float32, sh.device)
+        # the whole stride in one launch: padding columns hold sums nobody reads
+        ops.clip_sum_stack(stack, row, dscale, acc, n_clients=n)
+        packer.hold_slab(KIND_F32, [stack], sh.device)
+    sums = {KIND_F32: [(sh, ops.FoldedSum(acc, na.ACC_F32, n, sh.width))]}
+    for kind, (dsh, st) in dense.items():
+        if kind != KIND_F32:  # the plan's unit weights average the 8-byte buckets over all N
+            sums[kind] = [(dsh, st)]
+    results = agg._server_step(plan, sums, server_opt)
+    for kind, (dsh, st) in dense.items():
+        if kind != KIND_F32:
+            packer.hold_slab(kind, [st], dsh.device)
+    return agg._finish(plan, results)
+
+
+def client_norm2(agg, g32: Group, stack, row, n: int, device) -> np.ndarray:
+    """The clients' float64 squared update norms over the fp32 bucket's keys, on the host: one
+    ops.rownorm2_stack launch per run of keys (padding columns may hold another layout's values), one
+    copy — the round's one synchronisation —, the runs summed in key order."""
+    runs = key_runs(g32)
+    norms = agg.packer.device_bucket(("norm2", KIND_F32), (len(runs), n), torch.float64, device)
+    work_bytes = max(ops.rownorm_workspace(n, c1 - c0) for c0, c1 in runs)
+    work = agg.packer.device_bucket(("norm2_work", KIND_F32), (work_bytes,), torch.uint8, device)
+    for i, (c0, c1) in enumerate(runs):
+        ops.rownorm2_stack(stack, center=row, n_clients=n, col_begin=c0, n_cols=c1 - c0, out=norms[i], workspace=work)
+    host = norms.cpu().numpy()
+    norm2 = host[0].copy()
+    for part in host[1:]:
+        norm2 += part
+    return norm2
 
 
 def client_gram(agg, plan: BucketPlan, dense: dict, centre):

@@ -1,7 +1,8 @@
 """Strategy plugins with the reference's names (flearn/common/strategy/__init__.py:1-34).
 
 In scope (server reduce on the MI355X engine): AVG, AVGM, OPT, SGD, Prox, BN, LG, LG_R, Dyn,
-Distill; and, beyond the reference, the robust rules TrimmedMean, Median, Krum and MultiKrum (robust.py).  Out of scope (server-side model training): DF, MD, PAV — not
+Distill; and, beyond the reference, the robust rules TrimmedMean, Median, Krum, MultiKrum and
+NormClip (robust.py).  Out of scope (server-side model training): DF, MD, PAV — not
 provided; keep using flearn's for those.
 """
 from .avg import AVG
@@ -13,7 +14,7 @@ from .lg import LG
 from .lg_reverse import LG_R
 from .opt import OPT
 from .prox import Prox
-from .robust import Krum, Median, MultiKrum, TrimmedMean
+from .robust import Krum, Median, MultiKrum, NormClip, TrimmedMean
 from .sgd import SGD
 from .strategy import BaseEncrypt, ParentStrategy, Strategy
 from .utils import convert_to_np, convert_to_tensor
@@ -33,6 +34,7 @@ __all__ = [
     "Median",
     "Krum",
     "MultiKrum",
+    "NormClip",
     "ParentStrategy",
     "Strategy",
     "BaseEncrypt",

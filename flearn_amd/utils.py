@@ -6,7 +6,7 @@ import random
 import numpy as np
 import torch
 
-from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, Prox, TrimmedMean
+from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, NormClip, Prox, TrimmedMean
 
 __all__ = ["setup_strategy", "setup_seed", "base_strategy_lst", "OUT_OF_SCOPE"]
 
@@ -22,7 +22,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     `custom_strategy`, else SystemError.  Extra keyword arguments understood here:
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
     (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median),
-    f, m, center and server_opt (Krum / MultiKrum; f defaults to 0)."""
+    f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center and
+    server_opt (NormClip)."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -44,6 +45,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "krum": lambda: Krum(strategy_p.get("f", 0), strategy_p.get("server_opt"), strategy_p.get("center", "previous"), **eng),
         "multikrum": lambda: MultiKrum(strategy_p.get("f", 0), strategy_p.get("m"), strategy_p.get("server_opt"),
                                        strategy_p.get("center", "previous"), **eng),
+        "normclip": lambda: NormClip(strategy_p.get("tau"), strategy_p.get("quantile"), strategy_p.get("server_opt"),
+                                     strategy_p.get("center", "previous"), **eng),
     }
     if name in factories:
         return factories[name]()

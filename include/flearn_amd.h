@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 19
+#define FA_ABI_VERSION 20
 
 /* return codes */
 #define FA_OK 0
@@ -274,7 +274,8 @@ int fa_set_reduce_grid(int32_t grid);
 int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
- * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 call launched.  For tests and profilers that must know which kernel instantiation a
+ * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 /
+ * fa_clip_sum_f32 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -386,6 +387,53 @@ int64_t fa_gram_workspace(int32_t n_clients, int64_t n_cols);
 int fa_gram_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
                 int64_t col_begin, int64_t n_cols, void* workspace, int64_t workspace_bytes,
                 double* gram_out, void* stream);
+
+/* ---- robust aggregation: norm-clipped rounds -----------------------------
+ * Every client's update x_i - g is projected onto a ball of radius tau around the server's model g
+ * before the mean is taken (Sun et al. 2019; the clipping step of McMahan et al. 2018; the quantile
+ * radius of Andrew et al. 2021).  There is no reference counterpart: the rule takes the place of
+ * the weighted mean of flearn/common/strategy/strategy.py:123-129 in Strategy.server.  The norms
+ * are one streaming pass, the clipped sum a second one; the radius and the per-client scales are
+ * the caller's (flearn_amd/clip.py).  ABI 20.                                                     */
+#define FA_CLIP_MAX_CLIENTS 128
+/* Bytes of workspace fa_rownorm2_f32 needs for this shape on any device and under any
+ * fa_set_reduce_grid (one fp32 partial per client and block, at most 512 blocks); FA_ERR_ARG for
+ * n_clients outside [1, FA_CLIP_MAX_CLIENTS] or n_cols < 1.  HOST function, no HIP call.          */
+int64_t fa_rownorm_workspace(int32_t n_clients, int64_t n_cols);
+/* norm2_out[i] = sum over the window's columns k of y_i[k]^2, y_i[k] = fl32(stack[i][col_begin + k]
+ * - center[col_begin + k]) (one fp32 subtract; center: an fp32 row laid out like a stack row,
+ * 16-byte aligned, NULL: y = x).  Squares and sums are fp32 fused multiply-adds and adds in a fixed
+ * order (per lane, per wave, per block: plan_rownorm_window in csrc/fa_geometry.hpp), one fp32
+ * partial per client and block in `workspace`, summed per client in float64 in block order by a
+ * second kernel: the same inputs on the same device and grid give the same bits, and
+ * |error| <= (gamma(chain) + grid * 2^-52) * the exact sum of the same squares.  A non-finite value
+ * in row i makes norm2_out[i] non-finite and nothing else.  FA_ERR_ARG for a null stack / workspace
+ * / norm2_out, n_clients outside [1, FA_CLIP_MAX_CLIENTS], n_cols < 1 or a window outside the row;
+ * FA_ERR_ALIGN as for fa_gram_f32 (stack, center, workspace 16-byte aligned, norm2_out 8,
+ * row_stride / col_begin multiples of 4 elements); FA_ERR_SIZE for workspace_bytes <
+ * fa_rownorm_workspace (fa_last_error names the size).  Every error is decided before any HIP
+ * call.  Nothing outside norm2_out[0, n_clients) and the workspace is written; nothing is allocated
+ * or synchronised.  fa_set_reduce_grid applies (at most 512 blocks); fa_last_launch names the
+ * sweep's instantiation and grid, e.g. "rownorm_kernel<16,1,4,true>", launches = 2.              */
+int fa_rownorm2_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
+                    int64_t col_begin, int64_t n_cols, void* workspace, int64_t workspace_bytes,
+                    double* norm2_out, void* stream);
+/* acc_out[c] = yhat_0[c]; acc_out[c] = fl32(acc_out[c] + yhat_i[c]) for i = 1 .. n_clients - 1 in
+ * list order, with x = stack[i][col_begin + c], g = center[col_begin + c] and s = scale[i]:
+ *   s >= 1      : yhat = x (the row passes through, bits unchanged);
+ *   0 < s < 1   : yhat = fl32(g + fl32(s * fl32(x - g))), no fused multiply-add;
+ *   otherwise   : yhat = g, and row i is not read (s <= 0 or NaN: a non-finite upload).
+ * The accumulator is FA_ACC_F32's: fa_fold_finish divides it (FA_MODE_W32_DIV64, denom =
+ * n_clients) and runs the server update.  center (an fp32 row laid out like a stack row) and scale
+ * (fp32[n_clients], device memory) are required.  FA_ERR_ARG for a null pointer, n_clients outside
+ * [1, FA_CLIP_MAX_CLIENTS], n_cols < 0 or a window outside the row; FA_ERR_ALIGN as for fa_fold
+ * (stack, center, acc_out 16-byte aligned, scale 4, row_stride / col_begin multiples of 4
+ * elements).  Every error is decided before any HIP call.  Nothing outside acc_out[0, n_cols) is
+ * written; n_cols == 0 is a no-op.  fa_set_reduce_grid applies; fa_last_launch names the
+ * instantiation, e.g. "clip_sum_kernel<16,1,4,true>".                                            */
+int fa_clip_sum_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
+                    const float* scale, float* acc_out, int64_t col_begin, int64_t n_cols,
+                    void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

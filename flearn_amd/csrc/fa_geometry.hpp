@@ -1,5 +1,5 @@
 // fa_geometry.hpp — which kernel instantiation runs for a shape, and on what grid: the reduces, the
-// folds, the trimmed sums, the Gram matrix and the norm-clipped rounds.
+// folds, the trimmed sums, the Gram matrix, the norm-clipped rounds and their Gaussian noise.
 //
 // Plain C++17, pure integer decisions: no HIP, no globals, no device queries.  fa_reduce.hip asks
 // these functions for a Plan and turns it into a launch; tests/geometry_probe.cpp asks them on a
@@ -430,6 +430,32 @@ inline int64_t rownorm_workspace_bytes(int n_clients, int64_t n_cols) {
   int64_t blocks = n_cols > (int64_t)kRownormGridCap * 256 ? kRownormGridCap : row_chunks(n_cols < 1 ? 1 : n_cols);
   if (blocks > kRownormGridCap) blocks = kRownormGridCap;
   return blocks * n_clients * 4;
+}
+
+// Gaussian noise on an fp32 accumulator (fa_gauss_add_f32): gauss_add_kernel
+// is grid-stride over the window's 16-B quads, one quad per lane and step, kNoiseBlock lanes per
+// block.  The grid is the blocks that cover the quads once, at most kNoiseBlocksPerCU per CU (the
+// kernel's registers leave every wave slot of a CU usable: 8 four-wave blocks) or the forced grid.
+// A column's noise is a function of its absolute index alone, so the results do not depend on the
+// grid.  steps: the grid-stride steps of the busiest lane.
+constexpr int kNoiseBlock = 256;
+constexpr int kNoiseBlocksPerCU = 8;
+
+struct NoisePlan {
+  int64_t quads;   // 16-B quads of the window, a ragged last one included
+  int64_t blocks;  // kNoiseBlock-lane blocks that cover them once
+  int64_t grid;
+  int64_t steps;
+};
+
+inline NoisePlan plan_gauss_add(int64_t n_cols, int cus, int forced_grid) {
+  const int64_t quads = n_cols > 0 ? n_cols / 4 + (n_cols % 4 != 0) : 0;  // (no n_cols + 3: it may be INT64_MAX)
+  int64_t blocks = quads / kNoiseBlock + (quads % kNoiseBlock != 0);
+  if (blocks < 1) blocks = 1;
+  const int64_t cap = forced_grid > 0 ? forced_grid : (int64_t)cus * kNoiseBlocksPerCU;
+  int64_t grid = blocks < cap ? blocks : cap;
+  if (grid < 1) grid = 1;
+  return NoisePlan{quads, blocks, grid, ceil_div(blocks, grid)};
 }
 
 // The sorting network of trim_kernel_rows: Batcher's odd-even merge sort on NP = 2^q slots, as

@@ -1,4 +1,4 @@
-// fa_host.hpp — what the host units of the C ABI (fa_reduce.hip, fa_rows.hip, fa_gram.hip, fa_clip.hip, fa_transport.hip)
+// fa_host.hpp — what the host units of the C ABI (fa_reduce.hip, fa_rows.hip, fa_gram.hip, fa_clip.hip, fa_noise.hip, fa_transport.hip)
 // share: the per-thread error and launch-record state, the launch macros that name an
 // instantiation as they launch it, the op / mode dispatch, and the argument checks.  Internal:
 // inline functions and variables in namespace fa::host, nothing with a C name.
@@ -28,7 +28,7 @@ inline int fail(int code, const char* what) {
   return code;
 }
 
-// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 / fa_clip_sum_f32 call launched.  A launch
+// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 / fa_clip_sum_f32 / fa_gauss_add_f32 call launched.  A launch
 // stores a pointer and two integers; the name is built once per instantiation (a static of its
 // launch site, as resident_blocks_per_cu keeps its occupancy).
 struct LaunchRecord {

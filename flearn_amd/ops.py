@@ -5,7 +5,7 @@ engine (aggregator.py, streaming.py, serverstate.py) call.
 clients to a typed accumulator and `fold_finish` divides and updates a finished one; `trim_sum_stack`
 makes the accumulator of a robust round (per column, the sorted clients' middle values), `gram_stack`
 the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
-accumulator of a norm-clipped round.  `StackSum`
+accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
 """
@@ -422,6 +422,36 @@ def clip_sum_stack(stack: torch.Tensor, center: torch.Tensor, scale: torch.Tenso
     na.check(rc, "fa_clip_sum_f32")
 
 
+def gauss_add(acc: torch.Tensor, sigma: float, seed: int, sequence: int, *, col_begin: int = 0,
+              n_cols: int | None = None) -> None:
+    """acc[c] = fl32(acc[c] + fl32(sigma * z)) for c < n_cols (default: all of acc), z the standard
+    normal of the absolute column col_begin + c under (seed, sequence) (fa_gauss_add_f32; DESIGN.md
+    section 15, restated by tests/noise_ref.py), queued on torch's current stream.  acc: a contiguous
+    1-D fp32 device tensor, the window itself; col_begin (a multiple of 4, any size up to 2^63) only
+    enters the generator's counter.  seed and sequence are integers in [0, 2^64); the caller advances
+    sequence once per noised round, and the same (seed, sequence) repeats the noise.  sigma = 0 or an
+    empty window launches nothing."""
+    if (not isinstance(acc, torch.Tensor) or acc.dtype != torch.float32 or not acc.is_cuda or acc.dim() != 1
+            or not acc.is_contiguous()):
+        raise ValueError("acc must be a contiguous 1-D torch.float32 device tensor")
+    ncols = acc.numel() if n_cols is None else n_cols
+    for name, v in (("col_begin", col_begin), ("n_cols", ncols)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+    if ncols > acc.numel() or col_begin + ncols >= 2 ** 63:
+        raise ValueError("column window out of range")
+    for name, v in (("seed", seed), ("sequence", sequence)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 64:
+            raise ValueError(f"{name} must be an integer in [0, 2^64), got {v!r}")
+    with np.errstate(over="ignore"):
+        s32 = np.float32(sigma)
+    if not np.isfinite(s32) or s32 < 0:  # an fp32 argument: a finite double past fp32's range is refused too
+        raise ValueError(f"sigma must be finite in fp32 and >= 0, got {sigma!r}")
+    rc = na.lib().fa_gauss_add_f32(acc.data_ptr(), int(col_begin), int(ncols), float(s32), int(seed), int(sequence),
+                                   na.stream_handle(acc.device))
+    na.check(rc, "fa_gauss_add_f32")
+
+
 # ---------------------------------------------------------------------------------------------
 # a round's weighted sum, either way: what the engine's server step divides and updates
 # ---------------------------------------------------------------------------------------------
@@ -509,7 +539,7 @@ def apply_dyn(glob, h, theta, n_clients: int, alpha: float = 0.01, *, out32=None
 
 def set_reduce_grid(grid: int) -> int:
     """Blocks of the stack reduces (fp32 and float16), the folds, the trimmed sums, the Gram
-    matrix, the update norms and the clipped sum, process-wide (fa_set_reduce_grid): 0 = the library's
+    matrix, the update norms, the clipped sum and its noise, process-wide (fa_set_reduce_grid): 0 = the library's
     choice; fewer leave CUs to kernels running beside the reduce (RCCL's gather in the multi-GPU
     pipeline).  Returns the previous setting.  Results never depend on it."""
     L = na.load()

@@ -8,7 +8,8 @@ All need every client at once, on one device, with unit weights: they share thei
 Krum round is three steps: `client_gram` (ops.gram_stack per run of keys, to the host),
 krum.krum_select, and `selected_sums` (the selected rows, read where they are).  The clipped round
 measures each client's update norm (`client_norm2`: ops.rownorm2_stack per run of keys, to the host),
-takes its radius and scales from clip.py and sums the clipped uploads with ops.clip_sum_stack.
+takes its radius and scales from clip.py and sums the clipped uploads with ops.clip_sum_stack; a
+DP-FedAvg round then adds Gaussian noise to that sum (ops.gauss_add).
 """
 from __future__ import annotations
 
@@ -152,8 +153,11 @@ def ensemble_krum(agg, w_local_lst, f: int, m: int, key_lst=None, server_opt: Se
 
 
 # -- norm clipping ------------------------------------------------------------------------------
+_NOISE_AUDIT = ("noise_multiplier", "sigma", "seed", "sequence")  # clip.check_noise's tuple, as last_clip names it
+
+
 def ensemble_clipped(agg, w_local_lst, tau, quantile, key_lst=None, server_opt: ServerOptimizer | None = None,
-                     center=None):
+                     center=None, noise_multiplier=None, seed=None, sequence=0):
     """The mean of the uploads after each client's update x_i - g has been projected onto the ball of
     radius tau around `center` (g, the server's own model): norm clipping (Sun et al. 2019; the clipping
     step of McMahan et al. 2018).  Exactly one of tau (a float > 0) and quantile (q in (0, 1]: tau is
@@ -172,15 +176,33 @@ def ensemble_clipped(agg, w_local_lst, tau, quantile, key_lst=None, server_opt: 
     int64 buckets (BN counters) do not enter the norm and are averaged over all N clients.
     center=None: no clip, the round is that unit-weight mean itself.
 
+    noise_multiplier > 0 makes the round DP-FedAvg's (McMahan et al. 2018): after
+    the clipped sum and before the divide, one ops.gauss_add over the whole stride adds
+    fl32(sigma * z) to every column of the SUM, sigma = fl32(noise_multiplier * tau) — tau being the
+    most one client moves the sum by — and z the standard normal of (seed, sequence, column); the
+    mean's noise has standard deviation sigma / N.  Padding columns get noise nobody reads.  The caller
+    advances `sequence` once per noised round: the same (seed, sequence) repeats the noise.  With
+    noise_multiplier None or 0 nothing is launched and the round is the one above, bit for bit.
+    Float64 / int64 buckets (BN counters) are neither measured, clipped nor noised: they are outside
+    the guarantee.  So is everything else a guarantee needs — the accounting of (epsilon, delta), the
+    sampling of clients — and Philox is a statistical generator, not a cryptographic one.
+
     self.last_clip = {"norm2", "scale", "tau", "clipped", "replaced", "centered"} (host arrays; clipped:
-    the indices with s < 1, replaced: those with s = 0) is the audit.  Refused before anything is
+    the indices with s < 1, replaced: those with s = 0) is the audit; a round called with a
+    noise_multiplier also carries "noise_multiplier", "sigma", "seed" and "sequence", all None when no
+    noise was added (a multiplier of 0).  Refused before anything is
     queued: float16 buckets and FedDyn state (TypeError); several devices, group=, chunk_clients, more
     than 128 clients, a bad tau / quantile, uploads without an fp32 bucket and a centre lacking a key
-    (ValueError).  No finite norm under a quantile radius: ValueError after the norms."""
+    (ValueError); and noise with quantile=, with tau = inf, without a centre, without a seed, or with a
+    negative or non-finite multiplier (ValueError, clip.check_noise).  No finite norm under a quantile
+    radius: ValueError after the norms."""
     _refuse(agg, server_opt)
     plan = _plan_unit_weights(w_local_lst, key_lst, na.CLIP_MAX_CLIENTS, "clipped")
     n = plan.n_clients
     clip.check_radius(tau, quantile)
+    noise = clip.check_noise(noise_multiplier, seed, sequence, tau, quantile, center is not None)
+    # a round not asked for noise keeps the audit's six keys; one asked for it with a multiplier of 0 added none
+    audit = {} if noise_multiplier is None else dict(zip(_NOISE_AUDIT, noise or (None,) * len(_NOISE_AUDIT)))
     g32 = plan.groups.get(KIND_F32)
     if g32 is None or not any(s.numel > 0 for s in g32.segments):
         raise ValueError("norm clipping measures the fp32 bucket, and these uploads have none")
@@ -190,7 +212,7 @@ def ensemble_clipped(agg, w_local_lst, tau, quantile, key_lst=None, server_opt: 
         w_glob = agg.ensemble([1] * n, w_local_lst, key_lst, server_opt)
         none = np.empty(0, dtype=np.int64)
         agg.last_clip = {"norm2": None, "scale": None, "tau": None, "clipped": none, "replaced": none.copy(),
-                         "centered": False}
+                         "centered": False, **audit}
         return w_glob
     agg.last_plan = plan
     packer = agg.packer
@@ -203,12 +225,15 @@ def ensemble_clipped(agg, w_local_lst, tau, quantile, key_lst=None, server_opt: 
         radius = clip.clip_radius(norm2, tau, quantile)
         scale = clip.clip_scales(norm2, radius)
         agg.last_clip = {"norm2": norm2, "scale": scale, "tau": radius, "clipped": np.flatnonzero(scale < 1.0),
-                         "replaced": np.flatnonzero(scale == 0.0), "centered": True}
+                         "replaced": np.flatnonzero(scale == 0.0), "centered": True, **audit}
         dscale = packer.device_bucket(("clip_scale", KIND_F32), (n,), torch.float32, sh.device)
         dscale.copy_(torch.from_numpy(scale))
         acc = packer.device_bucket(("acc", KIND_F32), (g32.stride,), torch.float32, sh.device)
         # the whole stride in one launch: padding columns hold sums nobody reads
         ops.clip_sum_stack(stack, row, dscale, acc, n_clients=n)
+        if noise is not None:  # on the sum, before the divide; the padding's noise is never read
+            _, sigma, seed, sequence = noise
+            ops.gauss_add(acc, sigma, seed, sequence)
         packer.hold_slab(KIND_F32, [stack], sh.device)
     sums = {KIND_F32: [(sh, ops.FoldedSum(acc, na.ACC_F32, n, sh.width))]}
     for kind, (dsh, st) in dense.items():

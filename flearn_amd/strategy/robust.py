@@ -13,6 +13,7 @@ weight.  The result does not depend on the order of the uploads.
 from __future__ import annotations
 
 import math
+import secrets
 
 import numpy as np
 import torch
@@ -163,10 +164,23 @@ class NormClip(_RobustRound):
     fp32 tensors only (int64 / float64 buffers such as BN counters do not enter them and are averaged
     over all clients).  At most 128 clients per round, one device; client-data errors take
     server_exception's route.  `agg_weight` is required and ignored: a client must not be able to buy
-    influence with its own weight."""
+    influence with its own weight.
+
+    noise_multiplier > 0 (keyword-only, with a fixed tau) makes every round DP-FedAvg's (McMahan et al.
+    2018): Gaussian noise of standard deviation noise_multiplier * tau is added on the device to the
+    SUM of the clipped uploads, so the mean's is noise_multiplier * tau / N; `last_clip` then also
+    carries "noise_multiplier", "sigma", "seed" and "sequence".  The noise is a function of (seed,
+    sequence, column): seed=None draws secrets.randbits(64) at construction (`self.seed`), and
+    `self.sequence` advances by one per noised round.  REUSING A (seed, sequence) PAIR REPEATS THE
+    NOISE: a caller that restarts with an explicit seed must pass the next sequence.  Noise is refused
+    with quantile=, with tau = inf, and on a first round without `init_global` (which would run
+    unclipped).  The engine adds the noise and nothing else: the accounting of (epsilon, delta) and the
+    sampling of clients are the caller's, float64 / int64 buffers are not noised, and Philox is a
+    statistical generator, not a cryptographic one."""
 
     def __init__(self, tau=None, quantile=None, server_opt=None, center="previous", encrypt=None, output="reference",
-                 device=None, devices=None, group=None, chunk_clients=None):
+                 device=None, devices=None, group=None, chunk_clients=None, *, noise_multiplier=None, seed=None,
+                 sequence=0):
         from .. import clip
 
         super().__init__(encrypt, output, device, devices, group, chunk_clients)
@@ -176,6 +190,12 @@ class NormClip(_RobustRound):
         self.center = center
         self.server_opt = server_opt
         self._prev_glob = None
+        self.noise_multiplier = noise_multiplier
+        self.seed = secrets.randbits(64) if seed is None else seed
+        self.sequence = sequence
+        # the multiplier, and with noise on the radius, the seed and the sequence, refused here as the
+        # round would refuse them
+        self._noised = clip.check_noise(noise_multiplier, self.seed, sequence, self.tau, self.quantile, True) is not None
 
     @staticmethod
     def _copy(w_glob):
@@ -191,6 +211,9 @@ class NormClip(_RobustRound):
         """The engine's clipped round (Aggregator.ensemble_clipped).  agg_weight_lst is checked for
         presence by server_pre_processing and not used."""
         w_glob = self.engine.ensemble_clipped(w_local_lst, self.tau, self.quantile, key_lst, server_opt=server_opt,
-                                              center=self._prev_glob)
+                                              center=self._prev_glob, noise_multiplier=self.noise_multiplier,
+                                              seed=self.seed, sequence=self.sequence)
+        if self._noised:  # the round added its noise: never this (seed, sequence) again
+            self.sequence += 1
         self._prev_glob = self._copy(w_glob)  # a copy of its own: the caller may change what it is handed
         return w_glob

@@ -22,8 +22,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     `custom_strategy`, else SystemError.  Extra keyword arguments understood here:
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
     (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median),
-    f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center and
-    server_opt (NormClip)."""
+    f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
+    server_opt, noise_multiplier, seed and sequence (NormClip)."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -46,7 +46,9 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "multikrum": lambda: MultiKrum(strategy_p.get("f", 0), strategy_p.get("m"), strategy_p.get("server_opt"),
                                        strategy_p.get("center", "previous"), **eng),
         "normclip": lambda: NormClip(strategy_p.get("tau"), strategy_p.get("quantile"), strategy_p.get("server_opt"),
-                                     strategy_p.get("center", "previous"), **eng),
+                                     strategy_p.get("center", "previous"), **eng,
+                                     noise_multiplier=strategy_p.get("noise_multiplier"), seed=strategy_p.get("seed"),
+                                     sequence=strategy_p.get("sequence", 0)),
     }
     if name in factories:
         return factories[name]()

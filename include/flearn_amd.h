@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 20
+#define FA_ABI_VERSION 21
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_gauss_add_f32 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -434,6 +434,32 @@ int fa_rownorm2_f32(const float* stack, int64_t row_stride, int32_t n_clients, c
 int fa_clip_sum_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
                     const float* scale, float* acc_out, int64_t col_begin, int64_t n_cols,
                     void* stream);
+
+/* ---- Gaussian noise on the clipped sum: DP-FedAvg rounds -----------------
+ * A clipped round bounds every client's influence on the sum to tau; the Gaussian mechanism of
+ * DP-FedAvg (McMahan et al. 2018) adds N(0, sigma^2) noise to that sum, sigma = noise_multiplier *
+ * tau.  There is no reference counterpart.  The noise is counter-based, so a column's value is a
+ * function of (seed, sequence, absolute column) and of nothing else (tests/noise_ref.py restates it):
+ *   bits    : Philox4x32-10 (Salmon et al. 2011), key (seed & 0xffffffff, seed >> 32), counter
+ *             (q & 0xffffffff, q >> 32, sequence & 0xffffffff, sequence >> 32), q = column / 4;
+ *   uniform : u = ((word >> 9) + 0.5) * 2^-23, exact in fp32, never 0 or 1;
+ *   normal  : Box-Muller, words 0, 1 -> columns 4q, 4q + 1 as sqrt(-2 ln u_a) * (cos, sin)(2 pi u_b),
+ *             words 2, 3 -> columns 4q + 2, 4q + 3; fp32, |z| <= sqrt(48 ln 2) = 5.768.
+ * Philox is a statistical generator, not a cryptographic one; the privacy accounting is the
+ * caller's.  ABI 21.
+ *
+ * acc[c] = fl32(acc[c] + fl32(sigma * z(col_begin + c))) for c in [0, n_cols): acc points at the
+ * window's first column, col_begin is that column's absolute index in the bucket row (it only
+ * enters the counter and may exceed 2^32).  The caller advances `sequence` once per noised round:
+ * the same (seed, sequence) repeats the noise.  FA_ERR_ARG for a NULL acc with n_cols > 0, n_cols <
+ * 0, col_begin < 0 and a sigma that is negative, NaN or inf; FA_ERR_ALIGN for acc not 16-byte
+ * aligned or col_begin no multiple of 4.  Every error is decided before any HIP call.  n_cols == 0
+ * or sigma == 0 is a no-op that launches nothing (the accumulator's bits, a -0.0 included, stay).
+ * Nothing outside acc[0, n_cols) is written; nothing is allocated or synchronised.
+ * fa_set_reduce_grid applies (the results do not depend on it); fa_last_launch names
+ * "gauss_add_kernel".                                                                            */
+int fa_gauss_add_f32(float* acc, int64_t col_begin, int64_t n_cols, float sigma, uint64_t seed,
+                     uint64_t sequence, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

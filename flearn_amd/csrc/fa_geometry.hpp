@@ -1,6 +1,9 @@
 // fa_geometry.hpp — which kernel instantiation runs for a shape, and on what grid: the reduces, the
 // folds, the trimmed sums, the Gram matrix, the norm-clipped rounds and their Gaussian noise.
 //
+// And one numerics decision on a launch constant: whether the epilogues' reciprocal quotient is exact
+// for a weight sum (recip_quot_exact).
+//
 // Plain C++17, pure integer decisions: no HIP, no globals, no device queries.  fa_reduce.hip asks
 // these functions for a Plan and turns it into a launch; tests/geometry_probe.cpp asks them on a
 // CPU box (tests/test_geometry_plan.py).  Measured with tools/tune_reduce.hip on MI355X
@@ -8,6 +11,7 @@
 #pragma once
 
 #include <stdint.h>
+#include <string.h>
 
 #include <initializer_list>
 
@@ -53,6 +57,25 @@ constexpr int kBalancedV = 4, kBalancedU = 1;
 // 7.4e-7 at 512, 2.5e-6 at 1024 (a 6-element bias, MOON weights), 1.3e-6 at 2048 — so 256.
 // Columns whose terms nearly cancel are re-summed in order by the kernel's guard.
 constexpr int kSplitW = 4, kSplitD = 8, kSplitMaxN = 256;
+
+// The epilogues divide an fp32 sum x by the launch's weight sum d in double.  For a d with a short
+// significand the quotient's two-fma form on r = RN(1/d) (fa_numerics.hpp: quot) is RN(x / d) for
+// every fp32 x — proved in DESIGN.md §2 under exactly these conditions, so all three are kept
+// although longer denominators passed the exhaustive CPU run too:
+//   * d finite and non-zero;
+//   * 2^-100 <= |d| <= 2^100 (no product, remainder or correction leaves the normal double range
+//     for any fp32 x, subnormal x included);
+//   * d's significand has at most 27 significant bits: the low 26 bits of the mantissa field are 0.
+// Integer sample counts and unit weights summed (100.0, 3.0, ..., up to 2^27) qualify; 0.001 does
+// not and keeps the IEEE divide.
+inline bool recip_quot_exact(double d) {
+  uint64_t u;
+  memcpy(&u, &d, sizeof u);
+  const int exp = (int)((u >> 52) & 0x7ff) - 1023;  // finite non-zero normal: -1022 .. 1023
+  if (exp < -100 || exp > 100) return false;        // also 0, subnormals, infinities and NaN
+  if (exp == 100 && (u & 0xfffffffffffffull) != 0) return false;  // |d| <= 2^100
+  return (u & ((1ull << 26) - 1)) == 0;
+}
 
 // 1-KiB row pieces of a window of `ncols` elements, `per` of them in a 16-B load
 inline int64_t row_chunks(int64_t ncols, int per = 4) { return ((ncols + per - 1) / per + 63) / 64; }

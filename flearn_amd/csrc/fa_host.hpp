@@ -12,6 +12,7 @@
 #include <string>
 #include <type_traits>
 
+#include "fa_geometry.hpp"
 #include "fa_numerics.hpp"
 #include "flearn_amd.h"
 
@@ -185,6 +186,10 @@ template <typename T>
 int make_epi(const fa_epilogue* in, double denom, int n_reduced, float* out32, double* out64, Epi<T>* e,
              int64_t ncols = 0) {
   e->denom = (T)denom;
+  // the reciprocal quotient: double epilogues only (fp32 sums: kHasRecipQuot), and only where it is
+  // the IEEE quotient bit for bit
+  e->rq = sizeof(T) == 8 && recip_quot_exact(denom) ? 1 : 0;
+  e->rdenom = e->rq ? 1.0 / denom : 0.0;
   e->prev = nullptr;
   e->v = nullptr;
   e->h = nullptr;

@@ -123,7 +123,35 @@ struct Epi {
   double* out64;
   unsigned long long* trace;  // tuning only (reduce_kernel_rowmajor<..., TR = true>): phase timestamps
   T* v_out;                   // where the updated v goes; NULL: back into v (in place)
+  double rdenom;              // 1.0 / denom, rounded once on the host (quot)
+  int rq;                     // quot's reciprocal form is exact for this denom (fa::recip_quot_exact)
 };
+
+// Which quotient a launch takes is wave-uniform (e.rq), so the callers branch once per piece and
+// pass it down as RQ.  The reciprocal form exists for fp32 sums divided in double only.
+template <typename T, typename A>
+constexpr bool kHasRecipQuot = sizeof(T) == 8 && sizeof(A) == 4;
+
+// sum / denom in T.  RQ: the same double without the divide (13 f64 instructions on gfx950, a
+// v_rcp_f64 among them): two fma steps on x * (1/denom), bit-identical to IEEE x / denom for every
+// fp32 x when denom's significand has at most 27 bits and 2^-100 <= |denom| <= 2^100 — the proof is
+// in DESIGN.md §2, the rule in fa::recip_quot_exact (fa_geometry.hpp).  Zeros, infinities and NaN
+// come out of the first product as the divide would give them (the remainder step would turn an
+// infinity into NaN).
+template <typename T, typename A, int RQ>
+__device__ __forceinline__ T quot(const Epi<T>& e, A a) {
+  if constexpr (RQ != 0 && kHasRecipQuot<T, A>) {
+    const double x = (double)a, d = (double)e.denom;
+    const double q0 = x * e.rdenom;
+#ifdef FA_TUNE_QUOT_MUL  // tools/tune_reduce.hip's timing probe (rq = 2): the bare product, WRONG results
+    if constexpr (RQ == 2) return q0;
+#endif
+    const double q = __builtin_fma(__builtin_fma(-q0, d, x), e.rdenom, q0);
+    return (q0 == 0.0 || !__builtin_isfinite(q0)) ? q0 : q;
+  } else {
+    return (T)a / e.denom;
+  }
+}
 
 template <typename T>
 __device__ __forceinline__ T sign_of(T x) {
@@ -156,14 +184,14 @@ __device__ __forceinline__ T update(const Epi<T>& e, T g, T l, T& vv) {
 
 // divide and update one quad: a = its sums, l / vv = its loaded state in, updated state out (l:
 // FedDyn's h), w = the new global values
-template <typename T, int OP, typename A>
+template <typename T, int OP, typename A, int RQ = 0>
 __device__ __forceinline__ void epi_compute(const Epi<T>& e, const typename vec4<A>::type a,
                                             typename vec4<float>::type& l, typename vec4<T>::type& vv,
                                             typename vec4<T>::type& w) {
   if constexpr (OP == FA_OP_DYN) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const T g = (T)a[j] / e.denom;
+      const T g = quot<T, A, RQ>(e, a[j]);
       const T d = g * e.n - vv[j];                  // delta_theta = w_glob*N - theta   dyn.py:20-21
       const float hn = (float)((T)l[j] - e.c * d);  // h -= alpha/N * delta (fp32 h)    dyn.py:26
       const float ah = e.alpha32 * hn;              // alpha * h stays fp32              dyn.py:33
@@ -174,7 +202,7 @@ __device__ __forceinline__ void epi_compute(const Epi<T>& e, const typename vec4
   } else {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const T g = (T)a[j] / e.denom;  // np.divide(w_glob, np.sum(a))  strategy.py:127-129
+      const T g = quot<T, A, RQ>(e, a[j]);  // np.divide(w_glob, np.sum(a))  strategy.py:127-129
       T vj = vv[j];
       w[j] = update<T, OP>(e, g, (T)l[j], vj);
       vv[j] = vj;
@@ -355,21 +383,18 @@ __device__ __forceinline__ void epi_store(const Epi<T>& e, const EpiRsrc<T, OP>&
   if (!GUARD || e.out64) buf_store_tquad<double, XL>(r.r64, q, typename vec4<double>::type{(double)w[0], (double)w[1], (double)w[2], (double)w[3]});
 }
 
-template <typename T, int OP, typename A, bool GUARD = true, bool XL = false>
+template <typename T, int OP, typename A, bool GUARD = true, bool XL = false, int RQ = 0>
 __device__ __forceinline__ void epi_quad(const Epi<T>& e, const EpiRsrc<T, OP>& r, int q,
                                          const typename vec4<A>::type a, typename vec4<float>::type l,
                                          typename vec4<T>::type vv) {
   typename vec4<T>::type w;
-  epi_compute<T, OP, A>(e, a, l, vv, w);
+  epi_compute<T, OP, A, RQ>(e, a, l, vv, w);
   epi_store<T, OP, GUARD, XL>(e, r, q, l, vv, w);
 }
 
-template <typename T, int OP, typename A, int V, int STEP, int B, bool XL = false>
-__device__ __forceinline__ void finish_piece(const Epi<T>& e, int64_t qbase, int cols,
-                                             const typename vec4<A>::type (&acc)[V]) {
-  static_assert(V % B == 0, "batch must divide the slots");
-  if (cols <= 0) return;
-  const EpiRsrc<T, OP> r(e, qbase, cols);
+template <typename T, int OP, typename A, int V, int STEP, int B, bool XL, int RQ>
+__device__ __forceinline__ void finish_piece_rq(const Epi<T>& e, const EpiRsrc<T, OP>& r,
+                                                const typename vec4<A>::type (&acc)[V]) {
 #pragma unroll
   for (int b0 = 0; b0 < V; b0 += B) {
     typename vec4<float>::type l[B];
@@ -378,8 +403,25 @@ __device__ __forceinline__ void finish_piece(const Epi<T>& e, int64_t qbase, int
     for (int b = 0; b < B; ++b) epi_load<T, OP>(r, (int)threadIdx.x + (b0 + b) * STEP, l[b], vv[b]);
 #pragma unroll
     for (int b = 0; b < B; ++b)
-      epi_quad<T, OP, A, true, XL>(e, r, (int)threadIdx.x + (b0 + b) * STEP, acc[b0 + b], l[b], vv[b]);
+      epi_quad<T, OP, A, true, XL, RQ>(e, r, (int)threadIdx.x + (b0 + b) * STEP, acc[b0 + b], l[b], vv[b]);
   }
+}
+
+template <typename T, int OP, typename A, int V, int STEP, int B, bool XL = false>
+__device__ __forceinline__ void finish_piece(const Epi<T>& e, int64_t qbase, int cols,
+                                             const typename vec4<A>::type (&acc)[V]) {
+  static_assert(V % B == 0, "batch must divide the slots");
+  if (cols <= 0) return;
+  const EpiRsrc<T, OP> r(e, qbase, cols);
+  // (the plain mean only: a second copy of a fused epilogue costs the row-major kernels, which run
+  // at the register limit, spills to scratch, and the divide is a small part of those chains)
+  if constexpr (OP == FA_OP_MEAN && kHasRecipQuot<T, A>) {
+    if (e.rq == 1) return finish_piece_rq<T, OP, A, V, STEP, B, XL, 1>(e, r, acc);
+#ifdef FA_TUNE_QUOT_MUL
+    if (e.rq == 2) return finish_piece_rq<T, OP, A, V, STEP, B, XL, 2>(e, r, acc);
+#endif
+  }
+  finish_piece_rq<T, OP, A, V, STEP, B, XL, 0>(e, r, acc);
 }
 
 // acc + w*x on whole quads, written as <4 x T> IR operations: per-element scalar code gets packed

@@ -452,7 +452,9 @@ __device__ __forceinline__ void rowmajor_piece_geom(int64_t g0, int j, int64_t k
 // Dead ends, measured and removed (profiles/HISTORY.md §4): the next group's first loads issued
 // before this group's epilogue stores (finding 24); the last pieces' sums parked in LDS so that XL
 // fits KG = 4 (finding 23); a per-quad epilogue through finish_quad (finding 10).
-template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB, bool TR, bool XL>
+// EARLY / RQ: the group's tail (below); chosen per launch by the kernel.
+template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB, bool TR, bool XL,
+          bool EARLY = false, int RQ = 0>
 __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, int64_t row_bytes, int n,
                                                const typename P::w_t* __restrict__ w, int64_t g0, int64_t k,
                                                int64_t pc, int64_t pieces, int64_t nquads, int64_t ncols,
@@ -461,7 +463,10 @@ __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, in
   static_assert(KG % D == 0, "pipeline depth must divide the group size");
   typedef typename P::acc_t A;
   typedef typename vec4<A>::type AV;
-  const int voff = (int)threadIdx.x * 16;
+  int voff = (int)threadIdx.x * 16;
+  // the early tail's copy of the sweep derives its lane offsets per group: shared with the other
+  // copy across the kernel, one of them was spilled to scratch and reloaded inside the last row
+  if constexpr (EARLY) asm volatile("" : "+v"(voff));
   int64_t qb[KG];
   uint32_t bytes[KG];  // 4 x the piece's columns; 0: every access of this slot is dropped
 #pragma unroll
@@ -505,6 +510,17 @@ __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, in
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  // The group's tail: the last row and the epilogue.  EARLY (the plain fp32 mean into out32 alone,
+  // at least two rows; RQ: quot's form): in the last row a piece's sums are final once its step is
+  // consumed, and the next piece's loads are issued right after — so pieces 0 .. KG-2 are divided
+  // under those loads, in place (the fp32 results replace the sums: no registers added), and only
+  // the last piece's divide runs with nothing in flight.  Two quads at a time between scheduling
+  // barriers, as the sweep pins its steps.  The same arithmetic per element as finish_piece's; the
+  // stores stay at the group's end (findings 14 and 24: stores inside the read stream lose).
+  // The tail is a template argument and not a branch here: with two tails behind one sweep the
+  // register allocator spilled the sweep's lane offsets to scratch (DESIGN.md §4 finding 28).
+  static_assert(!EARLY || (OP == FA_OP_MEAN && sizeof(A) == 4), "early quotients: the plain fp32 mean");
+  constexpr int kQB = V >= 2 ? 2 : 1;  // quads divided between two scheduling barriers
   if (i < n) {  // last row: refills only inside the row
     const typename P::w_t wi = w[i];
 #pragma unroll
@@ -512,17 +528,78 @@ __device__ __forceinline__ void rowmajor_group(const char* __restrict__ base, in
 #pragma unroll
       for (int v = 0; v < V; ++v) acc[j][v] = quad_axpy<P>(acc[j][v], wi, x[j % D][v]);
       if (j + D < KG) FA_RM_LOAD(j % D, i, j + D);
+      if constexpr (EARLY) {
+        if (j + 1 < KG) {
+#pragma unroll
+          for (int v0 = 0; v0 < V; v0 += kQB) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int v = v0; v < v0 + kQB; ++v)
+#pragma unroll
+              for (int c = 0; c < 4; ++c) acc[j][v][c] = (A)quot<T, A, RQ>(e, acc[j][v][c]);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
     }
   }
 #undef FA_RM_LOAD
   if constexpr (TR) {
     if (threadIdx.x == 0 && gi < 7) e.trace[blockIdx.x * 16 + 1 + 2 * gi] = wall_clock64();
   }
+  if constexpr (EARLY) {  // (the kernel sends n == 1 to the other tail)
 #pragma unroll
-  for (int j = 0; j < KG; ++j) finish_piece<T, OP, A, V, 64 * W, EPIB, XL>(e, qb[j], (int)(bytes[j] / 4), acc[j]);
+    for (int j = 0; j + 1 < KG; ++j) {  // these hold their fp32 results
+      const __amdgpu_buffer_rsrc_t r32 = col_rsrc<float>(e.out32, qb[j], (int)(bytes[j] / 4));
+#pragma unroll
+      for (int v = 0; v < V; ++v) buf_store_tquad<float>(r32, (int)threadIdx.x + v * 64 * W, acc[j][v]);
+    }
+    if (bytes[KG - 1] > 0) {
+      const EpiRsrc<T, OP> r(e, qb[KG - 1], (int)(bytes[KG - 1] / 4));
+      finish_piece_rq<T, OP, A, V, 64 * W, EPIB, XL, RQ>(e, r, acc[KG - 1]);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < KG; ++j) finish_piece<T, OP, A, V, 64 * W, EPIB, XL>(e, qb[j], (int)(bytes[j] / 4), acc[j]);
+  }
   if constexpr (TR) {
     if (threadIdx.x == 0 && gi < 7) e.trace[blockIdx.x * 16 + 2 + 2 * gi] = wall_clock64();
   }
+}
+
+// A block's groups, under the tail the launch takes (wave-uniform; rowmajor_group): early quotients
+// for the plain fp32 mean of two or more rows into out32 alone, where the host chose the reciprocal
+// form (e.rq).  Measured on 100 x 25.6 M (tools/tune_reduce.hip set "quot", DESIGN.md §4 finding
+// 28): early reciprocal quotients -5..-6 us a launch; early IEEE divides +2.6 us (13 f64
+// instructions an element outlast the loads they sit under), so those launches keep the tail at the
+// group's end.  KG = 4 stands at 488 of the 512 registers with one sweep and a second copy of it
+// spilled: it keeps one tail too.
+// ED = false (tools/tune_reduce.hip only): every quotient at the group's end, as before finding 28.
+template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB, bool TR, bool XL, bool ED>
+__device__ __forceinline__ void rowmajor_groups(const char* __restrict__ base, int64_t row_bytes, int n,
+                                                const typename P::w_t* __restrict__ w, int64_t k, int64_t pc,
+                                                int64_t pieces, int64_t nquads, int64_t ncols, const Epi<T>& e,
+                                                typename vec4<float>::type (&x)[D][V]) {
+  typedef typename P::acc_t A;
+  int gi = 0;
+#define FA_RM_GROUPS(EARLY, RQ)                                                                               \
+  for (int64_t g0 = 0; g0 < k; g0 += KG)                                                                      \
+    rowmajor_group<P, T, OP, V, D, W, KG, NT, EPIB, TR, XL, EARLY, RQ>(base, row_bytes, n, w, g0, k, pc, pieces, \
+                                                                       nquads, ncols, gi++, e, x);
+  if constexpr (ED && OP == FA_OP_MEAN && kHasRecipQuot<T, A> && KG <= 3) {
+    if (n >= 2 && e.out64 == nullptr && e.rq == 1) {
+      FA_RM_GROUPS(true, 1)
+      return;
+    }
+#ifdef FA_TUNE_QUOT_MUL
+    if (n >= 2 && e.out64 == nullptr && e.rq == 2) {
+      FA_RM_GROUPS(true, 2)
+      return;
+    }
+#endif
+  }
+  FA_RM_GROUPS(false, 0)
+#undef FA_RM_GROUPS
 }
 
 // Row-major variant for blocks that own several pieces (k > 1: C2-C5-sized buckets).  The
@@ -558,10 +635,7 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_rowmajor(const float* __
   }
   static_assert(EPIB >= 1, "the piece epilogue batches at least one slot");
   typename vec4<float>::type x[D][V];  // the pipeline's slots
-  int gi = 0;
-  for (int64_t g0 = 0; g0 < k; g0 += KG)
-    rowmajor_group<P, T, OP, V, D, W, KG, NT, EPIB, TR, XL>(base, row_bytes, n, w, g0, k, pc, pieces, nquads, ncols,
-                                                            gi++, e, x);
+  rowmajor_groups<P, T, OP, V, D, W, KG, NT, EPIB, TR, XL, true>(base, row_bytes, n, w, k, pc, pieces, nquads, ncols, e, x);
 }
 
 }  // namespace fa

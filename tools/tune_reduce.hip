@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+// quot's timing probe (rq = 2: the bare product x * (1/d), WRONG results) exists in this tool only
+#define FA_TUNE_QUOT_MUL 1
 #include "fa_tune_device.hpp"
 
 #define CK(x)                                                                        \
@@ -278,6 +280,26 @@ __global__ __launch_bounds__(64 * W) void reduce_kernel_rowmajor_dfr(const float
     }
     pg0 = g0;
   }
+}
+
+// reduce_kernel_rowmajor with the group tail as a switch (set "quot", finding 28): ED = false keeps
+// every quotient at the group's end, the form before the early quotients; ED = true is the product.
+template <class P, typename T, int OP, int V, int D, int W, int KG, bool NT, int EPIB, bool TR, bool ED>
+__global__ __launch_bounds__(64 * W) void reduce_kernel_rowmajor_ed(const float* __restrict__ stack, int64_t stride,
+                                                                    int n, const typename P::w_t* __restrict__ w,
+                                                                    int64_t col0, int64_t ncols, Epi<T> e) {
+  const int64_t nquads = (ncols + 3) / 4;
+  const int64_t chunks = (nquads + 63) / 64;
+  const int64_t g = gridDim.x;
+  const int64_t k = (chunks + g * W * V - 1) / (g * W * V);
+  const int64_t pc = (chunks + g * k - 1) / (g * k);
+  const int64_t pieces = (chunks + pc - 1) / pc;
+  if constexpr (TR) {
+    if (threadIdx.x == 0) e.trace[blockIdx.x * 16] = wall_clock64();
+  }
+  typename vec4<float>::type x[D][V];
+  rowmajor_groups<P, T, OP, V, D, W, KG, NT, EPIB, TR, false, ED>(reinterpret_cast<const char*>(stack + col0), stride * 4,
+                                                                  n, w, k, pc, pieces, nquads, ncols, e, x);
 }
 
 // ---- tuning-only kernels measured in round 3 and NOT adopted (DESIGN.md §4 findings 17, 18) ----
@@ -701,6 +723,23 @@ Variant make_rowmajor(const float* stack, int64_t stride, int n, const float* w,
           true, {}};
 }
 
+// the plain mean's quotient forms (set "quot"): ED as above; rq 0 = IEEE divide, 1 = the exact
+// reciprocal form, 2 = the bare product (timing probe, not checked)
+template <int V, int D, int W, int KG, typename T, bool ED>
+Variant make_quot(const float* stack, int64_t stride, int n, const float* w, int64_t ncols, Epi<T> e, double bytes,
+                  int64_t grid, int rq) {
+  e.rq = rq;
+  e.rdenom = 1.0 / (double)e.denom;
+  char name[96];
+  snprintf(name, sizeof name, "rowmajor KG%d g%lld %s rq%d", KG, (long long)grid, ED ? "early" : "atend", rq);
+  return {name, bytes,
+          [=] {
+            hipLaunchKernelGGL((reduce_kernel_rowmajor_ed<AccF32, T, FA_OP_MEAN, V, D, W, KG, true, 2, false, ED>),
+                               dim3((unsigned)grid), dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
+          },
+          rq != 2, {}};
+}
+
 // row-major groups over the first (1 - tail) of the window, then W-KiB strips claimed from a
 // device counter (reduce_kernel_rowmajor_tail); the counter is cleared on the stream before every
 // launch (part of the timed work, as in the product)
@@ -763,7 +802,7 @@ Variant make_dfr(const float* stack, int64_t stride, int n, const float* w, int6
 
 // one traced launch of reduce_kernel_rowmajor<..., TR = true>: per group, the spread over blocks
 // of the sweep end and the epilogue end (us from the first block's start), and the epilogue length
-template <int V, int D, int W, int KG, int OP, typename T, int EB = 2>
+template <int V, int D, int W, int KG, int OP, typename T, int EB = 2, bool ED = true>
 void timeline(const float* stack, int64_t stride, int n, const float* w, int64_t ncols, Epi<T> e, int64_t grid) {
   const int64_t chunks = ((ncols + 3) / 4 + 63) / 64;
   if (grid > chunks) grid = chunks;
@@ -775,8 +814,13 @@ void timeline(const float* stack, int64_t stride, int n, const float* w, int64_t
   for (int rep = 0; rep < 2; ++rep) {
     CK(hipMemset(tr, 0, grid * 16 * 8));
     e.trace = tr;
-    hipLaunchKernelGGL((reduce_kernel_rowmajor<AccF32, T, OP, V, D, W, KG, true, EB, true>),
-                       dim3((unsigned)grid), dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
+    if constexpr (OP == FA_OP_MEAN && EB == 2) {  // (the _ed kernel has no XL form: the plain mean has none)
+      hipLaunchKernelGGL((reduce_kernel_rowmajor_ed<AccF32, T, OP, V, D, W, KG, true, EB, true, ED>),
+                         dim3((unsigned)grid), dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
+    } else {
+      hipLaunchKernelGGL((reduce_kernel_rowmajor<AccF32, T, OP, V, D, W, KG, true, EB, true>),
+                         dim3((unsigned)grid), dim3(64 * W), 0, 0, stack, stride, n, w, (int64_t)0, ncols, e);
+    }
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(h.data(), tr, grid * 16 * 8, hipMemcpyDeviceToHost));
     unsigned long long t0 = ~0ull;
@@ -790,8 +834,8 @@ void timeline(const float* stack, int64_t stride, int n, const float* w, int64_t
       printf("  %-12s min %8.1f  p10 %8.1f  med %8.1f  p90 %8.1f  max %8.1f us\n", what, us[0],
              us[us.size() / 10], us[us.size() / 2], us[us.size() * 9 / 10], us.back());
     };
-    printf("timeline V%d D%d W%d KG%d g%lld k%lld op%d epib%d rep %d\n", V, D, W, KG, (long long)grid, (long long)k,
-           OP, EB, rep);
+    printf("timeline V%d D%d W%d KG%d g%lld k%lld op%d epib%d %s rq%d rep %d\n", V, D, W, KG, (long long)grid,
+           (long long)k, OP, EB, ED ? "early" : "atend", e.rq, rep);
     stat(0, "start");
     {  // the last epilogue end per XCD (blocks are dispatched to the 8 XCDs round-robin)
       const int last = 2 + 2 * (groups - 1);
@@ -1046,6 +1090,16 @@ int main(int argc, char** argv) {
       RMXL(4, 4, true);
       RMXL(4, 4, false);
       RMXL(4, 4, true);
+    }
+  }
+  if (!strcmp(set, "quot") || !strcmp(set, "timeline")) {  // NS geometry: where and how the mean is divided
+    for (int rep = 0; rep < 2; ++rep) {
+      vs.push_back(make_quot<16, 1, 4, 3, double, false>(stack, stride, n, w, ncols, e, bytes, 192, 0));  // the parent's form
+      vs.push_back(make_quot<16, 1, 4, 3, double, false>(stack, stride, n, w, ncols, e, bytes, 192, 2));
+      vs.push_back(make_quot<16, 1, 4, 3, double, false>(stack, stride, n, w, ncols, e, bytes, 192, 1));
+      // (early IEEE divides, measured +2.6 us against the parent's form and removed: finding 28)
+      vs.push_back(make_quot<16, 1, 4, 3, double, true>(stack, stride, n, w, ncols, e, bytes, 192, 1));  // the product
+      vs.push_back(make_quot<16, 1, 4, 3, double, true>(stack, stride, n, w, ncols, e, bytes, 192, 2));
     }
   }
   if (!strcmp(set, "nostore")) {  // NS product geometry (KG 3) with and without its fp32 result stores
@@ -1453,7 +1507,15 @@ int main(int argc, char** argv) {
     } else if (op == FA_OP_ADAGRAD) {
       timeline<16, 1, 4, 4, FA_OP_ADAGRAD, double>(stack, stride, n, w, ncols, e, 192);
     } else if (kk % 3 == 0) {
-      timeline<16, 1, 4, 3, FA_OP_MEAN, double>(stack, stride, n, w, ncols, e, 192);
+      // the epilogue split (finding 28): the parent's form, the bare-product probe, the product
+      Epi<double> eq = e;
+      eq.rdenom = 1.0 / eq.denom;
+      timeline<16, 1, 4, 3, FA_OP_MEAN, double, 2, false>(stack, stride, n, w, ncols, eq, 192);
+      eq.rq = 2;
+      timeline<16, 1, 4, 3, FA_OP_MEAN, double, 2, false>(stack, stride, n, w, ncols, eq, 192);
+      eq.rq = 1;
+      timeline<16, 1, 4, 3, FA_OP_MEAN, double, 2, false>(stack, stride, n, w, ncols, eq, 192);
+      timeline<16, 1, 4, 3, FA_OP_MEAN, double, 2, true>(stack, stride, n, w, ncols, eq, 192);
     } else {
       timeline<16, 1, 4, 4, FA_OP_MEAN, double>(stack, stride, n, w, ncols, e, 192);
     }

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 21
+ABI_VERSION = 22
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -74,6 +74,7 @@ EXPORTS = (
     "fa_rownorm_workspace",
     "fa_rownorm2_f32",
     "fa_clip_sum_f32",
+    "fa_clip_fold_f32",
     "fa_gauss_add_f32",
     "fa_b64_decoded_size",
     "fa_b64_decode",
@@ -252,6 +253,7 @@ def load(require_gpu: bool = False):
                 "fa_rownorm_workspace": ([I32, I64], I64),
                 "fa_rownorm2_f32": ([P, I64, I32, P, I64, I64, P, I64, P, P], ctypes.c_int),
                 "fa_clip_sum_f32": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
+                "fa_clip_fold_f32": ([P, I64, I32, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_gauss_add_f32": ([P, I64, I64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),

@@ -8,7 +8,8 @@ clients (streaming.py); both end in the same server step (`Aggregator._server_st
 either kind of weighted sum (ops.StackSum, ops.FoldedSum).  The robust rounds, `ensemble_trimmed`
 (coordinate-wise trimmed mean and median), `ensemble_krum` (Krum / multi-Krum) and
 `ensemble_clipped` (norm clipping), are
-robustround.py's, bound on the class; they end in the same server step.
+robustround.py's, bound on the class; they end in the same server step.  `begin_clipped_round` and
+`ensemble_clipped_chunked` (clipstream.py) run the clipped round in chunks of clients.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
 (`ServerOptimizer`, `DynState`) serverstate.py, the small-host-round fast path smallround.py; every
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as na
-from . import robustround, smallround
+from . import clipstream, robustround, smallround
 from .bucketplan import BucketPlan, Shard, key_runs, make_plan, rank_width, select_keys  # noqa: F401
 from .dist import gather_columns
 from .ops import (FoldedSum, StackSum, _byte_range, _check_arrays, _check_cuda, _check_stack, _check_v_out,  # noqa: F401
@@ -74,6 +75,9 @@ class Aggregator:
     ensemble_trimmed = robustround.ensemble_trimmed
     ensemble_krum = robustround.ensemble_krum
     ensemble_clipped = robustround.ensemble_clipped
+    #: the streamed clipped / DP-FedAvg round (clipstream.py): any number of clients, a fixed tau
+    begin_clipped_round = clipstream.begin_clipped_round
+    ensemble_clipped_chunked = clipstream.ensemble_clipped_chunked
     _check_center = staticmethod(robustround._check_center)
     _center_row = robustround._center_row
     last_krum = None

@@ -1,11 +1,13 @@
 // fa_clip.hip — the norm-clipping entries of the C ABI (include/flearn_amd.h): fa_rownorm_workspace,
 // fa_rownorm2_f32 (fa_clip.hpp: the clients' squared update norms, one fp32 partial per client and
 // block, then their float64 sum) and fa_clip_sum_f32 (the sum of the clipped uploads, an FA_ACC_F32
-// accumulator for fa_fold_finish).  Host side only, as fa_gram.hip; a unit of its own so that it
+// accumulator for fa_fold_finish), and fa_clip_fold_f32 (fa_clipfold.hpp: the clipped sum of one chunk
+// of a streamed round, opening or continuing the accumulator).  Host side only, as fa_gram.hip; a unit of its own so that it
 // compiles beside the others and no existing kernel shares a unit with it.
 #include <string>
 
 #include "fa_clip.hpp"
+#include "fa_clipfold.hpp"
 #include "fa_geometry.hpp"
 #include "fa_host.hpp"
 
@@ -14,6 +16,7 @@ namespace {
 using namespace fa;
 using namespace fa::host;
 using namespace fa::clip;
+using fa::clipfold::clip_fold_kernel;
 
 int launch_rownorm(const RownormPlan& p, const float* stack, int64_t stride, int n, const float* center, int64_t col0,
                    int64_t ncols, float* partials, double* norm2_out, hipStream_t s) {
@@ -57,6 +60,26 @@ int launch_clip_sum(const Plan& p, const float* stack, int64_t stride, int n, co
   }
 #undef FA_CLIP_SUM
   return no_kernel("clip_sum_kernel");
+}
+
+int launch_clip_fold(const Plan& p, const float* stack, int64_t stride, int n, const float* center, const float* scale,
+                     const float* acc_in, float* acc_out, int64_t col0, int64_t ncols, hipStream_t s) {
+#define FA_CLIP_FOLD(V)                                                                                          \
+  case V:                                                                                                        \
+    FA_LAUNCH_AS(TInst, clip_fold_kernel, (V, kPieceChunks / (V * kFoldW), kFoldW, kNT), p.grid, 64 * kFoldW, s, \
+                 stack, stride, n, center, scale, acc_in, acc_out, col0, ncols);                                 \
+    return launch_check()
+  if (p.W == kFoldW && p.D == kPieceChunks / (p.V * kFoldW)) {
+    switch (p.V) {
+      FA_CLIP_FOLD(1);
+      FA_CLIP_FOLD(2);
+      FA_CLIP_FOLD(4);
+      FA_CLIP_FOLD(8);
+      FA_CLIP_FOLD(16);
+    }
+  }
+#undef FA_CLIP_FOLD
+  return no_kernel("clip_fold_kernel");
 }
 
 bool bad_window(int64_t row_stride, int64_t col_begin, int64_t n_cols) {
@@ -110,6 +133,26 @@ int fa_clip_sum_f32(const float* stack, int64_t row_stride, int32_t n_clients, c
   const Plan p = plan_fold_window(FA_ACC_F32, n_cols, device_cus(), g_reduce_grid.load(std::memory_order_relaxed));
   return launch_clip_sum(p, stack, row_stride, n_clients, center, scale, acc_out, col_begin, n_cols,
                          static_cast<hipStream_t>(stream));
+}
+
+int fa_clip_fold_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
+                     const float* scale, const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
+                     void* stream) {
+  g_last_launch = LaunchRecord{};
+  if (!stack || !center || !scale || !acc_out) return fail(FA_ERR_ARG, "null stack, center, scale or acc_out");
+  if (n_clients < 1) return fail(FA_ERR_ARG, "n_clients must be >= 1");
+  if (n_clients > FA_CLIP_MAX_CLIENTS) return fail(FA_ERR_ARG, "n_clients exceeds FA_CLIP_MAX_CLIENTS (128)");
+  if (n_cols < 0 || bad_window(row_stride, col_begin, n_cols)) return fail(FA_ERR_ARG, "bad column window");
+  if (!aligned_to(stack, 16) || row_stride % 4 != 0 || col_begin % 4 != 0)
+    return fail(FA_ERR_ALIGN, "row window not 16-B aligned (stack, and row_stride / col_begin in units of 4)");
+  if (!aligned_to(center, 16) || !aligned_to(acc_out, 16) || !aligned_to(acc_in, 16) || !aligned_to(scale, 4))
+    return fail(FA_ERR_ALIGN, "center, acc_in and acc_out must be 16-B aligned, scale 4-B aligned");
+  if (acc_in && acc_in != acc_out && overlaps(acc_in, acc_out, (size_t)n_cols * 4))
+    return fail(FA_ERR_ARG, "acc_out must be acc_in or an array not overlapping it");
+  if (n_cols == 0) return FA_OK;
+  const Plan p = plan_fold_window(FA_ACC_F32, n_cols, device_cus(), g_reduce_grid.load(std::memory_order_relaxed));
+  return launch_clip_fold(p, stack, row_stride, n_clients, center, scale, acc_in, acc_out, col_begin, n_cols,
+                          static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -422,6 +422,31 @@ def clip_sum_stack(stack: torch.Tensor, center: torch.Tensor, scale: torch.Tenso
     na.check(rc, "fa_clip_sum_f32")
 
 
+def clip_fold_stack(stack: torch.Tensor, center: torch.Tensor, scale: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+                    n_clients: int | None = None, col_begin: int = 0, n_cols: int | None = None) -> None:
+    """One chunk of a streamed clipped round (fa_clip_fold_f32), queued on torch's current stream:
+    acc_out[c] = acc_in[c] + the chunk's clipped uploads of column col_begin + c, added in list order
+    under clip_sum_stack's three-way rule.  acc_in None: the chunk opens the round and the call is
+    clip_sum_stack's (the first clipped upload initialises the sum).  Chunks chained through the
+    accumulator leave the bits of one clip_sum_stack over all their rows.  acc_out may be acc_in.
+    At most na.CLIP_MAX_CLIENTS clients per chunk."""
+    n, ncols = _check_f32_stack(stack, col_begin, n_cols, n_clients, na.CLIP_MAX_CLIENTS)
+    _check_center_row(center, stack, col_begin + ncols)
+    if (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or scale.device != stack.device
+            or not scale.is_contiguous() or scale.numel() < n):
+        raise ValueError(f"scale must be a contiguous torch.float32 tensor of at least {n} elements on the stack's device")
+    for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
+        if name == "acc_in" and t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.numel() < ncols
+                or not t.is_contiguous() or t.device != stack.device):
+            raise ValueError(f"{name} must be a contiguous torch.float32 tensor of at least {ncols} elements on the "
+                             "stack's device")
+    rc = na.lib().fa_clip_fold_f32(stack.data_ptr(), stack.stride(0), n, center.data_ptr(), scale.data_ptr(),
+                                   _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols, na.stream_handle(stack.device))
+    na.check(rc, "fa_clip_fold_f32")
+
+
 def gauss_add(acc: torch.Tensor, sigma: float, seed: int, sequence: int, *, col_begin: int = 0,
               n_cols: int | None = None) -> None:
     """acc[c] = fl32(acc[c] + fl32(sigma * z)) for c < n_cols (default: all of acc), z the standard

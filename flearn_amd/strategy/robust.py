@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .avg import AVG
+from .strategy import StrategyRound
 
 
 class _RobustRound(AVG):
@@ -217,3 +218,79 @@ class NormClip(_RobustRound):
             self.sequence += 1
         self._prev_glob = self._copy(w_glob)  # a copy of its own: the caller may change what it is handed
         return w_glob
+
+
+class StreamedNormClip(AVG):
+    """NormClip for any number of clients: the clipped (noise_multiplier: DP-FedAvg) round aggregated
+    in chunks of chunk_clients <= 128 clients (Aggregator.ensemble_clipped_chunked /
+    begin_clipped_round), with device memory O(chunk_clients x model) whatever the client count, and
+    bit-identical to NormClip(tau=...) on the rounds NormClip takes.  `server(uploads, round_)` takes the
+    whole list; `begin_round(round_)` returns a handle whose `add(upload | encoded str)` aggregates
+    uploads as they arrive and whose `finish()` returns what server() returns.  The engine's audit of
+    a round is `self.engine.last_clip` (NormClip's keys, the arrays over all clients in list order,
+    and "chunks").
+
+    Limits: a FIXED tau only (a streamed round cannot know a quantile of norms it has not seen), unit
+    weights (`agg_weight` is required and ignored), one device.  center, `init_global`, the undefended
+    first round without it, server_opt, noise_multiplier, seed and sequence are NormClip's:
+    seed=None draws secrets.randbits(64), `self.sequence` advances by one per noised round (at
+    finish()), and REUSING A (seed, sequence) PAIR REPEATS THE NOISE."""
+
+    def __init__(self, tau, server_opt=None, center="previous", encrypt=None, output="reference", device=None,
+                 chunk_clients=16, *, noise_multiplier=None, seed=None, sequence=0):
+        from .. import _native as na
+        from .. import clip
+
+        if (isinstance(chunk_clients, (bool, np.bool_)) or not isinstance(chunk_clients, (int, np.integer))
+                or not 1 <= chunk_clients <= na.CLIP_MAX_CLIENTS):
+            raise ValueError(f"chunk_clients must be an int in [1, {na.CLIP_MAX_CLIENTS}], got {chunk_clients!r}")
+        super().__init__(encrypt, output, device, None, None, int(chunk_clients))
+        self.tau, _ = clip.check_radius(tau, None)
+        if center != "previous":
+            raise ValueError(f'center must be "previous" (clipping needs a centre), got {center!r}')
+        self.center = center
+        self.server_opt = server_opt
+        self._prev_glob = None
+        self.noise_multiplier = noise_multiplier
+        self.seed = secrets.randbits(64) if seed is None else seed
+        self.sequence = sequence
+        self._noised = clip.check_noise(noise_multiplier, self.seed, sequence, self.tau, None, True) is not None
+
+    _copy = staticmethod(NormClip._copy)
+    init_global = NormClip.init_global
+
+    def _clip_args(self) -> dict:
+        return dict(center=self._prev_glob, chunk_clients=self.chunk_clients, noise_multiplier=self.noise_multiplier,
+                    seed=self.seed, sequence=self.sequence)
+
+    def _after_round(self, w_glob):
+        if self._noised:  # the round added its noise: never this (seed, sequence) again
+            self.sequence += 1
+        self._prev_glob = self._copy(w_glob)  # a copy of its own: the caller may change what it is handed
+        return w_glob
+
+    def server(self, ensemble_params_lst, round_):
+        """{"w_glob": the streamed clipped round's result}; client-data errors -> server_exception,
+        device errors propagate."""
+        return {"w_glob": self._ensemble_or_exit(ensemble_params_lst, server_opt=self.server_opt)}
+
+    def server_ensemble(self, agg_weight_lst, w_local_lst, key_lst=None, server_opt=None):
+        """The engine's streamed clipped round (Aggregator.ensemble_clipped_chunked).  agg_weight_lst is
+        checked for presence by server_pre_processing and not used."""
+        return self._after_round(self.engine.ensemble_clipped_chunked(w_local_lst, self.tau, key_lst,
+                                                                      server_opt=server_opt, **self._clip_args()))
+
+    def _round_done(self, w_glob, uploads):
+        return {"w_glob": self._after_round(w_glob)}
+
+    def begin_round(self, round_):
+        return _StreamedClipRound(self, round_)
+
+
+class _StreamedClipRound(StrategyRound):
+    """StreamedNormClip.begin_round's handle: StrategyRound over the engine's ClippedRoundAccumulator."""
+
+    def _begin(self, first_params):
+        s = self.strategy
+        self._acc = self._guard(lambda: s.engine.begin_clipped_round(s.tau, key_lst=None, server_opt=s.server_opt,
+                                                                     **s._clip_args()))

@@ -34,6 +34,9 @@ class RoundAccumulator:
     divide mode, the denominator and the output dtype come from resolve() on the whole weight list at
     finish().  `reorder` does not apply: a streamed round is always bit-exact."""
 
+    #: the device buffers device_bytes counts, by the first element of their tag
+    _device_tags = ("in", "acc", "out32", "out64", "dyn_g")
+
     def __init__(self, agg, key_lst=None, server_opt=None, chunk_clients: int = 16):
         if agg._dist:
             raise ValueError("a streamed round is not sharded over a process group (group=): use ensemble()")
@@ -155,14 +158,19 @@ class RoundAccumulator:
         self.max_stack_rows = max(self.max_stack_rows, len(ps))
         with torch.cuda.device(dev):
             for kind, parts in stacks.items():
-                g = plan.groups[kind]
                 _, stack = packer.dense_stack(plan, kind, parts, len(ps))  # the chunk stack
-                ak = acc_kind_of(kind, g.numerics.mode)
-                acc = agg.packer.device_bucket(("acc", kind), (g.stride,), _ACC_TORCH[ak], dev)
-                fold_stack(ak, stack, agg._weights(g.numerics, dev), self._acc.get(kind), acc, n_clients=len(ps))
-                self._acc[kind] = acc
-                packer.hold_slab(kind, [stack], dev)
+                self._fold_bucket(packer, plan.groups[kind], stack, len(ps))
         self._chunks += 1
+
+    def _fold_bucket(self, packer: Packer, g: Group, stack, n: int) -> None:
+        """One bucket's chunk stack (n rows, packed by `packer`) into its accumulator."""
+        agg, kind = self.agg, g.kind
+        dev = agg.device
+        ak = acc_kind_of(kind, g.numerics.mode)
+        acc = agg.packer.device_bucket(("acc", kind), (g.stride,), _ACC_TORCH[ak], dev)
+        fold_stack(ak, stack, agg._weights(g.numerics, dev), self._acc.get(kind), acc, n_clients=n)
+        self._acc[kind] = acc
+        packer.hold_slab(kind, [stack], dev)
 
     # -- the end of the round -----------------------------------------------------------------
     def _final_plan(self) -> BucketPlan:
@@ -206,7 +214,7 @@ class RoundAccumulator:
         for p in packers:
             for (tag, _dev), t in p._dev.items():
                 name = tag[0] if isinstance(tag, tuple) else tag
-                if name in ("in", "acc", "out32", "out64", "dyn_g") and id(t) not in seen:
+                if name in self._device_tags and id(t) not in seen:
                     seen.add(id(t))
                     total += t.numel() * t.element_size()
         return total

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 21
+#define FA_ABI_VERSION 22
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 / fa_gauss_add_f32 call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -434,6 +434,22 @@ int fa_rownorm2_f32(const float* stack, int64_t row_stride, int32_t n_clients, c
 int fa_clip_sum_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
                     const float* scale, float* acc_out, int64_t col_begin, int64_t n_cols,
                     void* stream);
+/* One chunk of a streamed clipped round (ABI 22): fa_clip_sum_f32 with a
+ * carried sum.  acc_in == NULL opens the round and is fa_clip_sum_f32 exactly (acc_out[c] =
+ * yhat_0[c], then the other rows added).  Otherwise acc_out[c] = acc_in[c]; acc_out[c] =
+ * fl32(acc_out[c] + yhat_i[c]) for i = 0 .. n_clients - 1 in list order, yhat by the same three-way
+ * rule (a row whose scale is <= 0 or NaN is not read).  The clipped sum is a running sum in list
+ * order, so chunks chained through the accumulator leave the bits of one fa_clip_sum_f32 over all
+ * their rows; n_clients in [1, FA_CLIP_MAX_CLIENTS] bounds one chunk, not the round.  acc_out may
+ * be acc_in (a column is read and written by the same lane); any other overlap of the two within
+ * n_cols elements is FA_ERR_ARG, as for fa_fold.  Other errors and alignment rules are
+ * fa_clip_sum_f32's, and acc_in must be 16-byte aligned.  Every error is decided before any HIP
+ * call.  Nothing outside acc_out[0, n_cols) is written and nothing outside acc_in[0, n_cols) is
+ * read; n_cols == 0 is a no-op.  fa_set_reduce_grid applies; fa_last_launch names the
+ * instantiation, e.g. "clip_fold_kernel<16,1,4,true>", launches = 1.                             */
+int fa_clip_fold_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
+                     const float* scale, const float* acc_in, float* acc_out, int64_t col_begin,
+                     int64_t n_cols, void* stream);
 
 /* ---- Gaussian noise on the clipped sum: DP-FedAvg rounds -----------------
  * A clipped round bounds every client's influence on the sum to tau; the Gaussian mechanism of

@@ -10,7 +10,7 @@ The hot path (Strategy.server -> server_ensemble) runs hand-written HIP kernels 
 through the C ABI in include/flearn_amd.h; there is no CPU fallback.
 """
 from .strategy import (AVG, AVGM, BN, LG, LG_R, OPT, SGD, BaseEncrypt, Distill, Dyn, Krum, Median, MultiKrum, NormClip,
-                       ParentStrategy, Prox, StreamedNormClip, Strategy, TrimmedMean)
+                       ParentStrategy, Prox, QuantizedAVG, StreamedNormClip, Strategy, TrimmedMean)
 from .strategy import convert_to_np, convert_to_tensor
 from .utils import base_strategy_lst, setup_seed, setup_strategy
 from .wire import Encrypt
@@ -35,6 +35,7 @@ __all__ = [
     "MultiKrum",
     "NormClip",
     "StreamedNormClip",
+    "QuantizedAVG",
     "Strategy",
     "ParentStrategy",
     "BaseEncrypt",

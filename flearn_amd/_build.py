@@ -10,7 +10,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 # the device units, one per entry group (each includes only the kernel families it launches)
-SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport", "fa_gram", "fa_clip", "fa_noise")]
+SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport", "fa_gram", "fa_clip", "fa_noise", "fa_quant")]
 HOST_SOURCES = [HERE / "csrc" / "fa_wire.cpp"]  # plain host C++ (g++), linked into the same .so
 DEPS = sorted((HERE / "csrc").glob("*.hpp"))  # every header: a new one cannot be forgotten
 MAX_COMPILE_JOBS = 8

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 22
+ABI_VERSION = 23
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -32,6 +32,7 @@ PREC_F32, PREC_F64 = 0, 1
 ACC_F32, ACC_F32_W64, ACC_F64, ACC_I64 = 0, 1, 2, 3  # fa_fold accumulator kinds (FA_ACC_*)
 TRIM_MAX_CLIENTS = 128  # fa_trim_sum's deepest client stack (FA_TRIM_MAX_CLIENTS)
 GRAM_MAX_CLIENTS = 128  # fa_gram_f32's (FA_GRAM_MAX_CLIENTS)
+Q8_BLOCK = 1024  # columns per scale of a quantized row (FA_Q8_BLOCK)
 CLIP_MAX_CLIENTS = 128  # fa_rownorm2_f32's and fa_clip_sum_f32's (FA_CLIP_MAX_CLIENTS)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
@@ -76,6 +77,7 @@ EXPORTS = (
     "fa_clip_sum_f32",
     "fa_clip_fold_f32",
     "fa_gauss_add_f32",
+    "fa_deq_fold_q8",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -255,6 +257,7 @@ def load(require_gpu: bool = False):
                 "fa_clip_sum_f32": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_clip_fold_f32": ([P, I64, I32, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_gauss_add_f32": ([P, I64, I64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, P], ctypes.c_int),
+                "fa_deq_fold_q8": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

@@ -9,7 +9,8 @@ either kind of weighted sum (ops.StackSum, ops.FoldedSum).  The robust rounds, `
 (coordinate-wise trimmed mean and median), `ensemble_krum` (Krum / multi-Krum) and
 `ensemble_clipped` (norm clipping), are
 robustround.py's, bound on the class; they end in the same server step.  `begin_clipped_round` and
-`ensemble_clipped_chunked` (clipstream.py) run the clipped round in chunks of clients.
+`ensemble_clipped_chunked` (clipstream.py) run the clipped round in chunks of clients;
+`ensemble_quantized` (quantround.py) sums int8 block-quantized uploads.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
 (`ServerOptimizer`, `DynState`) serverstate.py, the small-host-round fast path smallround.py; every
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _native as na
-from . import clipstream, robustround, smallround
+from . import clipstream, quantround, robustround, smallround
 from .bucketplan import BucketPlan, Shard, key_runs, make_plan, rank_width, select_keys  # noqa: F401
 from .dist import gather_columns
 from .ops import (FoldedSum, StackSum, _byte_range, _check_arrays, _check_cuda, _check_stack, _check_v_out,  # noqa: F401
@@ -82,6 +83,9 @@ class Aggregator:
     _center_row = robustround._center_row
     last_krum = None
     last_clip = None  # the last clipped round's audit
+    #: the round of int8 block-quantized uploads (quantround.py); last_quant: its audit
+    ensemble_quantized = quantround.ensemble_quantized
+    last_quant = None
 
     def __init__(self, device=None, output: str = "reference", workers: int = 8, devices=None, group=None,
                  reorder: bool = False, chunk_clients: int | None = None):

@@ -1,4 +1,4 @@
-// fa_host.hpp — what the host units of the C ABI (fa_reduce.hip, fa_rows.hip, fa_gram.hip, fa_clip.hip, fa_noise.hip, fa_transport.hip)
+// fa_host.hpp — what the host units of the C ABI (fa_reduce.hip, fa_rows.hip, fa_gram.hip, fa_clip.hip, fa_noise.hip, fa_quant.hip, fa_transport.hip)
 // share: the per-thread error and launch-record state, the launch macros that name an
 // instantiation as they launch it, the op / mode dispatch, and the argument checks.  Internal:
 // inline functions and variables in namespace fa::host, nothing with a C name.
@@ -29,7 +29,7 @@ inline int fail(int code, const char* what) {
   return code;
 }
 
-// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 / fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 call launched.  A launch
+// fa_last_launch (ABI 16): what the calling thread's last fa_reduce_* / fa_fold* / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 / fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 call launched.  A launch
 // stores a pointer and two integers; the name is built once per instantiation (a static of its
 // launch site, as resident_blocks_per_cu keeps its occupancy).
 struct LaunchRecord {
@@ -46,7 +46,7 @@ struct HInst {};  // the float16 family has no T
 template <class AT, typename T, auto... X>
 struct FInst {};  // the naming tag: fold_finish_kernel<A,T,OP>
 template <auto... A>
-struct TInst {};  // the naming tags: trim_kernel_rows<NP,W,NT>, gram_kernel_tile<NP,CEN,NT>, rownorm_kernel / clip_sum_kernel / clip_fold_kernel<V,D,W,NT>, trim_kernel_elem<T>
+struct TInst {};  // the naming tags: trim_kernel_rows<NP,W,NT>, gram_kernel_tile<NP,CEN,NT>, rownorm_kernel / clip_sum_kernel / clip_fold_kernel / deq_fold_kernel<V,D,W,NT>, trim_kernel_elem<T>
 template <class T>
 struct EInst {};
 

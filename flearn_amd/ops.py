@@ -5,7 +5,8 @@ engine (aggregator.py, streaming.py, serverstate.py) call.
 clients to a typed accumulator and `fold_finish` divides and updates a finished one; `trim_sum_stack`
 makes the accumulator of a robust round (per column, the sorted clients' middle values), `gram_stack`
 the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
-accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise.  `StackSum`
+accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise;
+`deq_fold_stack` adds a chunk of int8 block-quantized client rows to an fp32 accumulator.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
 """
@@ -445,6 +446,49 @@ def clip_fold_stack(stack: torch.Tensor, center: torch.Tensor, scale: torch.Tens
     rc = na.lib().fa_clip_fold_f32(stack.data_ptr(), stack.stride(0), n, center.data_ptr(), scale.data_ptr(),
                                    _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols, na.stream_handle(stack.device))
     na.check(rc, "fa_clip_fold_f32")
+
+
+def deq_fold_stack(stack_i8: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+                   center: torch.Tensor | None = None, col_begin: int = 0, n_cols: int | None = None,
+                   n_clients: int | None = None) -> None:
+    """One chunk of int8 block-quantized client rows added to an fp32 accumulator (fa_deq_fold_q8;
+    DESIGN.md section 17, restated by tests/quant_ref.py), queued on torch's current stream.  Per
+    column c of the window and row i in list order, every operation rounded to fp32:
+    x = scales[i, (col_begin + c) // 1024] * float(stack_i8[i, col_begin + c]); with `center` (an fp32
+    device row laid out like a stack row: delta uploads) x = center[col_begin + c] + x;
+    acc_out[c] = acc + weights[i] * x, acc starting from acc_in[c] — or, acc_in None, from row 0's
+    product: the chunk opens the round.  The bits are fold_stack's (na.ACC_F32) on the dequantized
+    rows, and fold_finish divides the accumulator.  stack_i8: int8 [N, stride], stride a multiple of
+    16; scales: fp32 [N, >= ceil((col_begin + n_cols) / 1024)]; weights: fp32 [>= N]; col_begin a
+    multiple of 1024.  acc_out may be acc_in.  No client cap."""
+    if (not isinstance(stack_i8, torch.Tensor) or stack_i8.dim() != 2 or stack_i8.stride(1) != 1
+            or not stack_i8.is_cuda):
+        raise ValueError("stack_i8 must be a 2-D device tensor with contiguous rows")
+    if stack_i8.dtype != torch.int8:
+        raise TypeError(f"stack_i8 must be torch.int8, got {stack_i8.dtype}")
+    n, ncols = _check_window(stack_i8.shape, col_begin, n_cols, n_clients)
+    dev = stack_i8.device
+    blocks = -(-(col_begin + ncols) // na.Q8_BLOCK)
+    if (not isinstance(scales, torch.Tensor) or scales.dtype != torch.float32 or scales.device != dev
+            or scales.dim() != 2 or scales.stride(1) != 1 or scales.shape[0] < n or scales.shape[1] < blocks):
+        raise ValueError(f"scales must be a torch.float32 [>= {n}, >= {blocks}] tensor with contiguous rows on the "
+                         "stack's device")
+    if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != dev
+            or not weights.is_contiguous() or weights.numel() < n):
+        raise ValueError(f"weights must be a contiguous torch.float32 tensor of at least {n} elements on the stack's device")
+    if center is not None:
+        _check_center_row(center, stack_i8, col_begin + ncols)
+    for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
+        if name == "acc_in" and t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.numel() < ncols
+                or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous torch.float32 tensor of at least {ncols} elements on the "
+                             "stack's device")
+    rc = na.lib().fa_deq_fold_q8(stack_i8.data_ptr(), stack_i8.stride(0), n, scales.data_ptr(), scales.stride(0),
+                                 weights.data_ptr(), _ptr(center), _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols,
+                                 na.stream_handle(dev))
+    na.check(rc, "fa_deq_fold_q8")
 
 
 def gauss_add(acc: torch.Tensor, sigma: float, seed: int, sequence: int, *, col_begin: int = 0,

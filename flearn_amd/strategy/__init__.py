@@ -2,7 +2,7 @@
 
 In scope (server reduce on the MI355X engine): AVG, AVGM, OPT, SGD, Prox, BN, LG, LG_R, Dyn,
 Distill; and, beyond the reference, the robust rules TrimmedMean, Median, Krum, MultiKrum and
-NormClip and StreamedNormClip (robust.py).  Out of scope (server-side model training): DF, MD, PAV — not
+NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 block-quantized uploads).  Out of scope (server-side model training): DF, MD, PAV — not
 provided; keep using flearn's for those.
 """
 from .avg import AVG
@@ -14,6 +14,7 @@ from .lg import LG
 from .lg_reverse import LG_R
 from .opt import OPT
 from .prox import Prox
+from .quantized import QuantizedAVG
 from .robust import Krum, Median, MultiKrum, NormClip, StreamedNormClip, TrimmedMean
 from .sgd import SGD
 from .strategy import BaseEncrypt, ParentStrategy, Strategy
@@ -36,6 +37,7 @@ __all__ = [
     "MultiKrum",
     "NormClip",
     "StreamedNormClip",
+    "QuantizedAVG",
     "ParentStrategy",
     "Strategy",
     "BaseEncrypt",

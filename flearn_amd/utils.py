@@ -6,7 +6,7 @@ import random
 import numpy as np
 import torch
 
-from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, NormClip, Prox, StreamedNormClip, TrimmedMean
+from .strategy import AVG, AVGM, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, NormClip, Prox, QuantizedAVG, StreamedNormClip, TrimmedMean
 
 __all__ = ["setup_strategy", "setup_seed", "base_strategy_lst", "OUT_OF_SCOPE"]
 
@@ -23,7 +23,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
     (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median),
     f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
-    server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile)."""
+    server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
+    server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8")."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -54,6 +55,9 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
             **{k: v for k, v in eng.items() if k in ("output", "device")}, chunk_clients=strategy_p.get("chunk_clients", 16),
             noise_multiplier=strategy_p.get("noise_multiplier"), seed=strategy_p.get("seed"),
             sequence=strategy_p.get("sequence", 0)),
+        "avg_q8": lambda: QuantizedAVG(
+            strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False),
+            strategy_p.get("seed"), **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}),
     }
     if name in factories:
         return factories[name]()

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 22
+#define FA_ABI_VERSION 23
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -476,6 +476,34 @@ int fa_clip_fold_f32(const float* stack, int64_t row_stride, int32_t n_clients, 
  * "gauss_add_kernel".                                                                            */
 int fa_gauss_add_f32(float* acc, int64_t col_begin, int64_t n_cols, float sigma, uint64_t seed,
                      uint64_t sequence, void* stream);
+
+/* ---- int8 block-quantized uploads (ABI 23) -------------------------------
+ * A quantized client row is one int8 code per column and one fp32 scale per FA_Q8_BLOCK columns of
+ * the row (block b covers columns [1024 b, 1024 b + 1024)); all 256 codes are legal.  There is no
+ * reference counterpart.  fa_deq_fold_q8 adds one chunk of n_clients quantized rows to an fp32
+ * accumulator without expanding them in memory.  Per column c of the window and row i, every
+ * operation rounded to fp32 and none contracted:
+ *   x   = fl32(scales[i * scale_stride + (col_begin + c) / 1024] * float(stack[i * row_stride + col_begin + c]))
+ *   x   = fl32(center[col_begin + c] + x)                      when center != NULL (delta uploads)
+ *   acc = fl32(acc + fl32(weights[i] * x))                     in list order
+ * acc starts from acc_in[c]; acc_in == NULL opens the round: acc = fl32(weights[0] * x_0), the other
+ * rows added.  These are fa_fold's (FA_ACC_F32) bits on the dequantized rows, an all -0.0 column and
+ * fp32 subnormals included.  row_stride is in bytes (= columns), scale_stride in floats per client
+ * row; center is indexed by absolute column like the stack, acc_in / acc_out from 0 at col_begin.
+ * acc_out may be acc_in.  Weights and scales are read from device memory per row: no client cap.
+ * FA_ERR_ARG: a NULL stack / scales / weights / acc_out, n_clients < 1, n_cols < 0, a window
+ * outside the row or whose last block is past scale_stride, or acc_in overlapping acc_out within
+ * n_cols elements without equalling it.  FA_ERR_ALIGN: stack / center / acc_in / acc_out not
+ * 16-byte aligned, row_stride no multiple of 16, col_begin no multiple of FA_Q8_BLOCK, scales /
+ * weights not 4-byte aligned.  Every error is decided before any HIP call.  n_cols == 0 is a no-op
+ * that launches nothing.  Code rows are read through a range rounded up to 4 columns (inside the
+ * row); nothing outside acc_out[0, n_cols) is written.  fa_set_reduce_grid applies; fa_last_launch
+ * names the instantiation, e.g. "deq_fold_kernel<4,4,4,true>", launches = 1.                      */
+#define FA_Q8_BLOCK 1024
+int fa_deq_fold_q8(const int8_t* stack, int64_t row_stride, int32_t n_clients, const float* scales,
+                   int64_t scale_stride, const float* weights, const float* center,
+                   const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
+                   void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

@@ -10,7 +10,7 @@ either kind of weighted sum (ops.StackSum, ops.FoldedSum).  The robust rounds, `
 `ensemble_clipped` (norm clipping), are
 robustround.py's, bound on the class; they end in the same server step.  `begin_clipped_round` and
 `ensemble_clipped_chunked` (clipstream.py) run the clipped round in chunks of clients;
-`ensemble_quantized` (quantround.py) sums int8 block-quantized uploads.
+`ensemble_quantized` (quantround.py) sums int8 or int4 block-quantized uploads.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
 (`ServerOptimizer`, `DynState`) serverstate.py, the small-host-round fast path smallround.py; every
@@ -83,7 +83,9 @@ class Aggregator:
     _center_row = robustround._center_row
     last_krum = None
     last_clip = None  # the last clipped round's audit
-    #: the round of int8 block-quantized uploads (quantround.py); last_quant: its audit
+    #: the round of int8 / int4 block-quantized uploads (quantround.py); last_quant: its audit.  A 4-bit
+    #: round's audit carries "bits": 4; an int8 round's has no "bits" key (its dict is what it was before
+    #: 4-bit rounds existed): read the width as last_quant.get("bits", 8)
     ensemble_quantized = quantround.ensemble_quantized
     last_quant = None
 

@@ -6,7 +6,8 @@ clients to a typed accumulator and `fold_finish` divides and updates a finished 
 makes the accumulator of a robust round (per column, the sorted clients' middle values), `gram_stack`
 the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
 accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise;
-`deq_fold_stack` adds a chunk of int8 block-quantized client rows to an fp32 accumulator.  `StackSum`
+`deq_fold_stack` adds a chunk of int8 block-quantized client rows to an fp32 accumulator and
+`deq_fold_q4_stack` one of int4 rows, two codes per byte.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
 """
@@ -461,14 +462,35 @@ def deq_fold_stack(stack_i8: torch.Tensor, scales: torch.Tensor, weights: torch.
     rows, and fold_finish divides the accumulator.  stack_i8: int8 [N, stride], stride a multiple of
     16; scales: fp32 [N, >= ceil((col_begin + n_cols) / 1024)]; weights: fp32 [>= N]; col_begin a
     multiple of 1024.  acc_out may be acc_in.  No client cap."""
-    if (not isinstance(stack_i8, torch.Tensor) or stack_i8.dim() != 2 or stack_i8.stride(1) != 1
-            or not stack_i8.is_cuda):
-        raise ValueError("stack_i8 must be a 2-D device tensor with contiguous rows")
-    if stack_i8.dtype != torch.int8:
-        raise TypeError(f"stack_i8 must be torch.int8, got {stack_i8.dtype}")
-    n, ncols = _check_window(stack_i8.shape, col_begin, n_cols, n_clients)
-    dev = stack_i8.device
-    blocks = -(-(col_begin + ncols) // na.Q8_BLOCK)
+    _deq_fold("fa_deq_fold_q8", "stack_i8", torch.int8, 1, na.Q8_BLOCK, stack_i8, scales, weights, acc_in, acc_out, center,
+              col_begin, n_cols, n_clients)
+
+
+def deq_fold_q4_stack(stack_u8: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+                      center: torch.Tensor | None = None, n_clients: int | None = None, col_begin: int = 0,
+                      n_cols: int | None = None) -> None:
+    """deq_fold_stack for int4 block-quantized rows (fa_deq_fold_q4; DESIGN.md section 18, restated by
+    tests/quant4_ref.py).  stack_u8: uint8 [N, stride bytes], stride a multiple of 16, holding
+    2 * stride columns per row: column c is a two's-complement nibble of byte c // 2, the low one for
+    even c.  Columns (col_begin, n_cols, the centre's and the accumulators' indices) are elements.
+    x = scales[i, (col_begin + c) // 128] * float(nibble), the rest as deq_fold_stack; scales: fp32
+    [N, >= ceil((col_begin + n_cols) / 128)], each 0 or >= 2^-100; col_begin a multiple of 2048.  The
+    bits are fold_stack's (na.ACC_F32) on the dequantized rows."""
+    _deq_fold("fa_deq_fold_q4", "stack_u8", torch.uint8, 2, na.Q4_BLOCK, stack_u8, scales, weights, acc_in, acc_out, center,
+              col_begin, n_cols, n_clients)
+
+
+def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_in, acc_out, center, col_begin, n_cols, n_clients):
+    """The checks and the call deq_fold_stack and deq_fold_q4_stack share: `stack` holds `per_byte`
+    columns per byte and one scale per `block` columns."""
+    if (not isinstance(stack, torch.Tensor) or stack.dim() != 2 or stack.stride(1) != 1
+            or not stack.is_cuda):
+        raise ValueError(f"{what} must be a 2-D device tensor with contiguous rows")
+    if stack.dtype != dtype:
+        raise TypeError(f"{what} must be {dtype}, got {stack.dtype}")
+    n, ncols = _check_window((stack.shape[0], stack.shape[1] * per_byte), col_begin, n_cols, n_clients)
+    dev = stack.device
+    blocks = -(-(col_begin + ncols) // block)
     if (not isinstance(scales, torch.Tensor) or scales.dtype != torch.float32 or scales.device != dev
             or scales.dim() != 2 or scales.stride(1) != 1 or scales.shape[0] < n or scales.shape[1] < blocks):
         raise ValueError(f"scales must be a torch.float32 [>= {n}, >= {blocks}] tensor with contiguous rows on the "
@@ -477,7 +499,7 @@ def deq_fold_stack(stack_i8: torch.Tensor, scales: torch.Tensor, weights: torch.
             or not weights.is_contiguous() or weights.numel() < n):
         raise ValueError(f"weights must be a contiguous torch.float32 tensor of at least {n} elements on the stack's device")
     if center is not None:
-        _check_center_row(center, stack_i8, col_begin + ncols)
+        _check_center_row(center, stack, col_begin + ncols)
     for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
         if name == "acc_in" and t is None:
             continue
@@ -485,10 +507,10 @@ def deq_fold_stack(stack_i8: torch.Tensor, scales: torch.Tensor, weights: torch.
                 or not t.is_contiguous() or t.device != dev):
             raise ValueError(f"{name} must be a contiguous torch.float32 tensor of at least {ncols} elements on the "
                              "stack's device")
-    rc = na.lib().fa_deq_fold_q8(stack_i8.data_ptr(), stack_i8.stride(0), n, scales.data_ptr(), scales.stride(0),
-                                 weights.data_ptr(), _ptr(center), _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols,
-                                 na.stream_handle(dev))
-    na.check(rc, "fa_deq_fold_q8")
+    rc = getattr(na.lib(), entry)(stack.data_ptr(), stack.stride(0), n, scales.data_ptr(), scales.stride(0),
+                                  weights.data_ptr(), _ptr(center), _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols,
+                                  na.stream_handle(dev))
+    na.check(rc, entry)
 
 
 def gauss_add(acc: torch.Tensor, sigma: float, seed: int, sequence: int, *, col_begin: int = 0,

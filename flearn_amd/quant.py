@@ -1,5 +1,5 @@
-"""Int8 block-quantized uploads: the format, its checks, and the client's
-quantizer and dequantizer.  Host-side numpy only, no device code.
+"""Int8 and int4 block-quantized uploads (DESIGN.md sections 17 and 18): the formats, their checks,
+and the client's quantizer and dequantizer.  Host-side numpy only, no device code.
 
 A quantized entry of upload["params"] replaces an fp32 tensor of shape S by a plain dict
 
@@ -11,25 +11,71 @@ x - g, g the server's previous global model in fp32, and the client's value is
 fl32(g + fl32(scale * q)).  In a quantized upload every fp32 tensor is quantized, tensors of other
 dtypes (int64 BN counters, float64) are sent plain, float16 is refused.
 
+The 4-bit entry (bits=4) packs two codes into a byte and scales blocks of 128:
+
+    {"q4": uint8 ndarray [ceil(numel / 2)], "shape": tuple S, "scale": float32 ndarray [ceil(numel / 128)],
+     "block": 128, "delta": bool}
+
+Element e (C order) is a nibble of byte e >> 1, the low one for even e; codes are two's complement,
+-8 ... 7, all 16 legal; block b covers elements [128 b, 128 b + 128); the value and `delta` are q8's.
+A scale is finite and either zero or >= Q4_MIN_SCALE = 2^-100: scale / 16 is then exact, which the
+device kernel relies on (it converts a nibble in place as 16 q and multiplies by scale / 16).  The
+quantizer leaves an odd tensor's spare high nibble 0; on receipt that nibble is ignored, whatever it
+holds (it is no element: dequantize_entry drops it, and on the device it lands in a padding column
+nobody reads).  One round's uploads are all of one width.
+
 Block-wise absmax scaling as in Dettmers et al. (ICLR 2022); quantized client updates as in FedPAQ
 (Reisizadeh et al., AISTATS 2020); the stochastic rounding is QSGD's (Alistarh et al., NeurIPS 2017).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
 BLOCK = 1024  # FA_Q8_BLOCK: one wave-chunk of fa_deq_fold_q8
+Q4_BLOCK = 128  # FA_Q4_BLOCK: a sixteenth of fa_deq_fold_q4's wave-chunk
+Q4_MIN_SCALE = np.float32(2.0 ** -100)  # FA_Q4_MIN_SCALE: the smallest non-zero scale of a 4-bit entry
 _F32 = np.dtype(np.float32)
+_BLOCK_OF = {8: BLOCK, 4: Q4_BLOCK}
+_LEVELS = {8: 127, 4: 7}
 
 
-def n_blocks(numel: int) -> int:
-    return -(-int(numel) // BLOCK)
+def n_blocks(numel: int, block: int = BLOCK) -> int:
+    return -(-int(numel) // block)
 
 
 def is_entry(v) -> bool:
-    """v is (shaped like) a quantized entry: a dict with a "q8"."""
-    return isinstance(v, dict) and "q8" in v
+    """v is (shaped like) a quantized entry: a dict with a "q8" or a "q4"."""
+    return isinstance(v, dict) and ("q8" in v or "q4" in v)
+
+
+def bits_of(e) -> int:
+    """The code width of a quantized entry."""
+    return 4 if "q4" in e else 8
+
+
+def entry_shape(e) -> tuple:
+    """The shape of the tensor an entry stands for."""
+    return tuple(e["shape"]) if "q4" in e else tuple(e["q8"].shape)
+
+
+def pack_nibbles(codes: np.ndarray) -> np.ndarray:
+    """int8 codes in [-8, 7], flat, as uint8 [ceil(n / 2)]: even elements in the low nibbles, an odd
+    count's spare high nibble 0."""
+    u = codes.astype(np.uint8) & np.uint8(0xF)
+    if u.size & 1:
+        u = np.append(u, np.uint8(0))
+    return u[0::2] | (u[1::2] << 4)
+
+
+def unpack_nibbles(q4: np.ndarray, numel: int) -> np.ndarray:
+    """pack_nibbles' inverse: the first `numel` sign-extended nibbles of a uint8 array, as int8."""
+    out = np.empty(2 * q4.size, dtype=np.int8)
+    out[0::2] = (q4 << 4).view(np.int8) >> 4
+    out[1::2] = q4.view(np.int8) >> 4
+    return out[:numel]
 
 
 def is_quantized(params) -> bool:
@@ -53,6 +99,8 @@ def check_entry(key, e, client=None):
     NaN or inf, and a missing field; TypeError for a q8 that is no int8 array (a device-resident one
     included) and a scale that is no float32 array."""
     where = f"key {key!r}" if client is None else f"client {client} key {key!r}"
+    if "q4" in e:
+        return _check_entry4(where, e)
     for f in ("q8", "scale", "block", "delta"):
         if f not in e:
             raise ValueError(f"{where}: quantized entry lacks {f!r}")
@@ -68,28 +116,73 @@ def check_entry(key, e, client=None):
         raise TypeError(f"{where}: scale must be float32, got {scale.dtype}")
     if scale.ndim != 1 or scale.shape[0] != n_blocks(q8.size):
         raise ValueError(f"{where}: {q8.size} codes need {n_blocks(q8.size)} scales, got shape {tuple(scale.shape)}")
-    if not (np.isfinite(scale).all() and (scale >= 0).all()):  # -0.0 passes: it is a zero
+    if not _scales_ok(scale, 8):
         raise ValueError(f"{where}: scales must be finite and >= 0")
     return np.ascontiguousarray(q8), np.ascontiguousarray(scale), bool(e["delta"])
 
 
+def _check_entry4(where: str, e):
+    """check_entry for a 4-bit entry: (q4 as a C-contiguous uint8 array, scale, delta).  Beyond q8's
+    refusals: a missing or malformed shape and a code count other than ceil(numel / 2) (ValueError), a
+    q4 that is no uint8 array (TypeError), a scale in (0, Q4_MIN_SCALE) (ValueError).  An odd tensor's
+    spare high nibble is not looked at."""
+    for f in ("q4", "shape", "scale", "block", "delta"):
+        if f not in e:
+            raise ValueError(f"{where}: quantized entry lacks {f!r}")
+    if "q8" in e:
+        raise ValueError(f"{where}: an entry carries q4 or q8 codes, not both")
+    if isinstance(e["block"], bool) or not isinstance(e["block"], (int, np.integer)) or int(e["block"]) != Q4_BLOCK:
+        raise ValueError(f"{where}: block must be {Q4_BLOCK} for 4-bit codes, got {e['block']!r}")
+    if not isinstance(e["delta"], (bool, np.bool_)):
+        raise ValueError(f"{where}: delta must be a bool, got {e['delta']!r}")
+    shape = e["shape"]
+    if not isinstance(shape, (tuple, list)) or not all(
+            isinstance(d, (int, np.integer)) and not isinstance(d, bool) and d >= 0 for d in shape):
+        raise ValueError(f"{where}: shape must be a tuple of non-negative ints, got {shape!r}")
+    numel = int(np.prod(shape, dtype=np.int64))
+    q4 = _host_array(e["q4"], f"{where} q4")
+    if q4.dtype != np.uint8:
+        raise TypeError(f"{where}: q4 must be uint8 (two codes per byte), got {q4.dtype}")
+    if q4.ndim != 1 or q4.shape[0] != (numel + 1) // 2:
+        raise ValueError(f"{where}: {numel} elements need {(numel + 1) // 2} code bytes, got shape {tuple(q4.shape)}")
+    scale = _host_array(e["scale"], f"{where} scale")
+    if scale.dtype != _F32:
+        raise TypeError(f"{where}: scale must be float32, got {scale.dtype}")
+    if scale.ndim != 1 or scale.shape[0] != n_blocks(numel, Q4_BLOCK):
+        raise ValueError(f"{where}: {numel} elements need {n_blocks(numel, Q4_BLOCK)} scales, got shape {tuple(scale.shape)}")
+    if not _scales_ok(scale, 4):
+        raise ValueError(f"{where}: 4-bit scales must be finite and either 0 or >= 2^-100")
+    return np.ascontiguousarray(q4), np.ascontiguousarray(scale), bool(e["delta"])
+
+
+def _scales_ok(scale: np.ndarray, bits: int) -> bool:
+    """Finite and >= 0 (-0.0 passes: it is a zero); 4-bit: and none in (0, Q4_MIN_SCALE)."""
+    ok = np.isfinite(scale).all() and (scale >= 0).all()
+    return bool(ok and (bits == 8 or ((scale == 0) | (scale >= Q4_MIN_SCALE)).all()))
+
+
 # -- the client's side -----------------------------------------------------------------------------
-def _blocks(flat: np.ndarray) -> np.ndarray:
-    """flat padded with zeros to whole blocks, as [blocks, 1024]"""
-    nb = n_blocks(flat.size)
-    if flat.size == nb * BLOCK:
-        return flat.reshape(nb, BLOCK)
-    out = np.zeros(nb * BLOCK, dtype=flat.dtype)
+def _blocks(flat: np.ndarray, block: int = BLOCK) -> np.ndarray:
+    """flat padded with zeros to whole blocks, as [blocks, block]"""
+    nb = n_blocks(flat.size, block)
+    if flat.size == nb * block:
+        return flat.reshape(nb, block)
+    out = np.zeros(nb * block, dtype=flat.dtype)
     out[: flat.size] = flat
-    return out.reshape(nb, BLOCK)
+    return out.reshape(nb, block)
 
 
-def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=None) -> dict:
-    """One fp32 array as a quantized entry.  Per block: amax = max|x|, s = fl32(amax / 127), codes
+def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=None, bits: int = 8) -> dict:
+    """One fp32 array as a quantized entry.  bits=4: blocks of 128, s = fl32(amax / 7), codes clipped
+    to -7 ... 7 and packed two per byte, a block with s < 2^-100 gets scale 0 and codes 0, and
+    |dequantized - x| <= s * (0.5 + 2^-20).  bits=8, per block: amax = max|x|, s = fl32(amax / 127), codes
     clip(rint(fl32(x / s)), -127, 127) (round half to even); s == 0 (an all-zero block, or amax / 127
     underflowing) gives codes 0 and scale 0.  stochastic: x / s is rounded up with probability equal
     to its fractional part (unbiased), with `rng` (a numpy.random.Generator).  center: x - center is
     quantized, in fp32, and the entry is marked delta.  Non-finite input: ValueError."""
+    if bits not in _BLOCK_OF:
+        raise ValueError(f"bits must be 8 or 4, got {bits!r}")
+    block, top = _BLOCK_OF[bits], _LEVELS[bits]
     x = np.asarray(x)
     if x.dtype != _F32:
         raise TypeError(f"only float32 arrays are quantized, got {x.dtype}")
@@ -103,9 +196,9 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
             flat = flat - np.ascontiguousarray(c, dtype=np.float32).reshape(-1)
     if not np.isfinite(flat).all():
         raise ValueError("non-finite values cannot be quantized")
-    b = _blocks(flat)
-    s = (np.abs(b).max(axis=1, initial=np.float32(0)) / np.float32(127)).astype(np.float32)
-    live = s > 0
+    b = _blocks(flat, block)
+    s = (np.abs(b).max(axis=1, initial=np.float32(0)) / np.float32(top)).astype(np.float32)
+    live = s > 0 if bits == 8 else s >= Q4_MIN_SCALE
     r = np.zeros_like(b)
     np.divide(b, s[:, None], out=r, where=live[:, None])
     if stochastic:
@@ -115,15 +208,23 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
         q = lo + (rng.random(r.shape) < (r - lo))
     else:
         q = np.rint(r)
-    q8 = np.clip(q, -127, 127).astype(np.int8).reshape(-1)[: flat.size].reshape(shape)
-    return {"q8": q8, "scale": np.where(live, s, np.float32(0)).astype(np.float32), "block": BLOCK,
-            "delta": center is not None}
+    codes = np.clip(q, -top, top).astype(np.int8).reshape(-1)[: flat.size]
+    scale = np.where(live, s, np.float32(0)).astype(np.float32)
+    if bits == 4:
+        return {"q4": pack_nibbles(codes), "shape": tuple(shape), "scale": scale, "block": block,
+                "delta": center is not None}
+    return {"q8": codes.reshape(shape), "scale": scale, "block": block, "delta": center is not None}
 
 
 def dequantize_entry(e, center=None, key=None) -> np.ndarray:
     """fl32(scale[b] * float(q)), and fl32(center + that) for a delta entry: the client's values."""
-    q8, scale, delta = check_entry(key, e)
-    x = (_blocks(q8.reshape(-1).astype(np.float32)) * scale[:, None]).astype(np.float32).reshape(-1)[: q8.size]
+    codes, scale, delta = check_entry(key, e)
+    shape = entry_shape(e)
+    if "q4" in e:
+        codes = unpack_nibbles(codes, int(np.prod(shape, dtype=np.int64)))
+    block = _BLOCK_OF[bits_of(e)]
+    with np.errstate(over="ignore"):  # a scale near the top of the range: the product is +-inf, as on the device
+        x = (_blocks(codes.reshape(-1).astype(np.float32), block) * scale[:, None]).astype(np.float32).reshape(-1)[: codes.size]
     if delta:
         if center is None:
             raise ValueError(f"key {key!r}: a delta entry needs the centre it was taken against")
@@ -131,14 +232,16 @@ def dequantize_entry(e, center=None, key=None) -> np.ndarray:
         if c.size != x.size:
             raise ValueError(f"center[{key!r}] has {c.size} elements, the entry has {x.size}")
         x = (c + x).astype(np.float32)
-    return x.reshape(q8.shape)
+    return x.reshape(shape)
 
 
-def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None) -> dict:
+def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None, bits: int = 8) -> dict:
     """A state dict (numpy arrays or host torch tensors) as a quantized upload's params: every fp32
     tensor becomes a quantized entry (quantize_array), tensors of other dtypes are passed on as numpy
     arrays, float16 raises TypeError.  center: a w_glob-like dict; its values, cast to fp32, are
-    subtracted before quantizing and the entries are marked delta=True."""
+    subtracted before quantizing and the entries are marked delta=True.  bits: 8 or 4."""
+    if bits not in _BLOCK_OF:
+        raise ValueError(f"bits must be 8 or 4, got {bits!r}")
     if stochastic and rng is None:
         raise ValueError("stochastic rounding needs rng (a numpy.random.Generator)")
     out = {}
@@ -154,7 +257,7 @@ def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None) -> 
             if k not in center:
                 raise ValueError(f"center has no key {k!r}")
             c = np.asarray(_host_array(center[k], f"center[{k!r}]"), dtype=np.float32)
-        out[k] = quantize_array(a, c, stochastic, rng)
+        out[k] = quantize_array(a, c, stochastic, rng, bits)
     return out
 
 
@@ -181,16 +284,18 @@ def _dtype_name(v) -> str:
 
 
 def check_round(w_local_lst, keys):
-    """(qkeys, delta, entries, scales) of a round of quantized uploads over the selected `keys`, or
-    client-data errors.  qkeys: the selected keys that are quantized, in order; delta: the round's
-    flag; entries[i][key] = (q8, scale) as checked host arrays; scales[i]: client i's scales of all
-    qkeys in order, one array.  ValueError: a key quantized by some clients and plain in others, a
+    """(qkeys, delta, entries, scales, bits) of a round of quantized uploads over the selected `keys`,
+    or client-data errors.  qkeys: the selected keys that are quantized, in order; delta: the round's
+    flag; entries[i][key] = (codes, scale) as checked host arrays (q8: int8 of the tensor's shape, q4:
+    the packed uint8 bytes); scales[i]: client i's scales of all qkeys in order, one array; bits: the
+    round's code width, 8 or 4.  ValueError: q4 and q8 entries in one round (across clients or keys),
+    a key quantized by some clients and plain in others, a
     plain fp32 tensor, mixed delta flags, codes of different shapes, and check_entry's; TypeError:
     float16 tensors, and check_entry's.  A well-formed numpy entry costs a few attribute reads; a
     client's scales are looked at once, together."""
     qkeys = [k for k in keys if is_entry(w_local_lst[0][k])]
     qset = set(qkeys)
-    delta = None
+    delta = bits = None
     entries, scales = [], []
     shapes = {}
     for i, w in enumerate(w_local_lst):
@@ -206,22 +311,38 @@ def check_round(w_local_lst, keys):
                     raise ValueError(f"client {i} key {k!r}: a plain fp32 tensor in a quantized upload "
                                      "(every fp32 tensor is quantized)")
                 continue
-            q8, sc, d = v.get("q8"), v.get("scale"), v.get("delta")
-            if not (type(q8) is np.ndarray and type(sc) is np.ndarray and q8.dtype == np.int8 and sc.dtype == _F32
-                    and sc.ndim == 1 and sc.shape[0] == n_blocks(q8.size) and type(v.get("block")) is int
-                    and v["block"] == BLOCK and type(d) is bool and q8.flags.c_contiguous and sc.flags.c_contiguous):
-                q8, sc, d = check_entry(k, v, i)  # raises what is wrong, or hands back the entry as host arrays
+            if bits is None:
+                bits = bits_of(v)
+            elif bits_of(v) != bits:
+                raise ValueError(f"client {i} key {k!r}: {bits_of(v)}-bit codes in a round of {bits}-bit uploads "
+                                 "(a round's uploads are all q8 or all q4)")
+            if bits == 4:
+                q8, sc, d, shape = v.get("q4"), v.get("scale"), v.get("delta"), v.get("shape")
+                if not (type(q8) is np.ndarray and type(sc) is np.ndarray and q8.dtype == np.uint8 and sc.dtype == _F32
+                        and type(shape) is tuple and all(type(n) is int and n >= 0 for n in shape) and "q8" not in v
+                        and q8.ndim == 1 and q8.shape[0] == (math.prod(shape) + 1) // 2 and sc.ndim == 1
+                        and sc.shape[0] == n_blocks(math.prod(shape), Q4_BLOCK) and type(v.get("block")) is int
+                        and v["block"] == Q4_BLOCK and type(d) is bool and q8.flags.c_contiguous and sc.flags.c_contiguous):
+                    q8, sc, d = check_entry(k, v, i)  # raises what is wrong, or hands back the packed bytes as host arrays
+                    shape = entry_shape(v)
+            else:
+                q8, sc, d = v.get("q8"), v.get("scale"), v.get("delta")
+                if not (type(q8) is np.ndarray and type(sc) is np.ndarray and q8.dtype == np.int8 and sc.dtype == _F32
+                        and sc.ndim == 1 and sc.shape[0] == n_blocks(q8.size) and type(v.get("block")) is int
+                        and v["block"] == BLOCK and type(d) is bool and q8.flags.c_contiguous and sc.flags.c_contiguous):
+                    q8, sc, d = check_entry(k, v, i)  # raises what is wrong, or hands back the entry as host arrays
+                shape = q8.shape
             if delta is None:
                 delta = d
             elif d != delta:
                 raise ValueError(f"client {i} key {k!r}: delta={d} in a round of delta={delta} uploads")
-            if q8.shape != shapes.setdefault(k, q8.shape):
-                raise ValueError(f"client {i} key {k!r}: codes of shape {q8.shape} do not match client 0's {shapes[k]}")
+            if shape != shapes.setdefault(k, shape):
+                raise ValueError(f"client {i} key {k!r}: codes of shape {shape} do not match client 0's {shapes[k]}")
             mine[k] = (q8, sc)
         cat = np.concatenate([mine[k][1] for k in qkeys]) if qkeys else np.zeros(0, np.float32)
-        if not (np.isfinite(cat).all() and (cat >= 0).all()):
+        if not _scales_ok(cat, bits or 8):
             for k in qkeys:
                 check_entry(k, w[k], i)  # names the key
         entries.append(mine)
         scales.append(cat)
-    return qkeys, bool(delta), entries, scales
+    return qkeys, bool(delta), entries, scales, bits or 8

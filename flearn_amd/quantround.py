@@ -1,7 +1,9 @@
 """The quantized round of the engine, bound on Aggregator as `ensemble_quantized` (DESIGN.md
-section 17): uploads whose fp32 tensors are int8 block-quantized entries (quant.py) are summed by
-ops.deq_fold_stack from a 1-byte-per-parameter device stack — the codes are never expanded to fp32
-in memory — and the round ends in the server step every round ends in (Aggregator._server_step).
+sections 17 and 18): uploads whose fp32 tensors are int8 or int4 block-quantized entries (quant.py)
+are summed by ops.deq_fold_stack / ops.deq_fold_q4_stack from a device stack of one byte, or half a
+byte, per parameter — the codes are never expanded to fp32 in memory — and the round ends in the
+server step every round ends in (Aggregator._server_step).  The two widths differ in their layout
+constants (_LAYOUT) and in how a key's codes are indexed; the round is one.
 """
 from __future__ import annotations
 
@@ -30,75 +32,86 @@ def _refuse(agg, server_opt) -> None:
         raise ValueError(f"chunk_clients must be an int >= 1 or None, got {k!r}")
 
 
+# per code width: (columns per scale, columns the row stride is a multiple of, columns per byte, the
+# stack's dtype, the staging buffers' tag, the device entry)
+_LAYOUT = {8: (quant.BLOCK, quant.BLOCK, 1, torch.int8, "q8", ops.deq_fold_stack),
+           4: (quant.Q4_BLOCK, na.Q4_CHUNK, 2, torch.uint8, "q4", ops.deq_fold_q4_stack)}
+
+
 def _stand_ins(w_local_lst, keys, qkeys, entries):
     """The uploads with every quantized entry replaced by a zero-strided fp32 array of its shape (no
     memory behind it): what make_plan plans the round's numerics, key order and 8-byte buckets from."""
     as_torch = any(isinstance(w_local_lst[0][k], torch.Tensor) for k in keys if k not in entries[0])
     zero_t, zero_n = torch.zeros((), dtype=torch.float32), np.float32(0)
-    stand = {k: (zero_t.expand(entries[0][k][0].shape) if as_torch else np.broadcast_to(zero_n, entries[0][k][0].shape))
-             for k in qkeys}
+    shapes = {k: quant.entry_shape(w_local_lst[0][k]) for k in qkeys}
+    stand = {k: (zero_t.expand(shapes[k]) if as_torch else np.broadcast_to(zero_n, shapes[k])) for k in qkeys}
     if len(qkeys) == len(keys):
         one = {k: stand[k] for k in keys}
         return [one] * len(w_local_lst)
     return [{k: stand[k] if k in stand else w[k] for k in keys} for w in w_local_lst]
 
 
-def _q8_plan(plan: BucketPlan) -> BucketPlan:
-    """`plan` with its fp32 group laid out for fa_deq_fold_q8: every segment starts on a 1024-column
-    boundary (one scale block never spans two keys) and the stride is a multiple of 1024.  Kept in
-    the base plan's memo: make_plan reuses plans across rounds."""
-    qp = plan.memo.get("q8plan")
+def _q_plan(plan: BucketPlan, bits: int) -> BucketPlan:
+    """`plan` with its fp32 group laid out for fa_deq_fold_q8 / _q4: every segment starts on a scale
+    block's boundary (1024 / 128 columns: one scale block never spans two keys) and the stride is a
+    multiple of 1024 / 2048 columns.  Kept in the base plan's memo: make_plan reuses plans across rounds."""
+    block, chunk, _, _, tag, _ = _LAYOUT[bits]
+    qp = plan.memo.get(tag + "plan")
     if qp is None:
         g = plan.groups[KIND_F32]
         segs, off = [], 0
         for s in g.segments:
             segs.append(Segment(s.key, s.shape, s.numel, off, s.src_dtype))
-            off += padded_span(s.numel, quant.BLOCK)
+            off += padded_span(s.numel, block)
+        off = -(-off // chunk) * chunk
         groups = dict(plan.groups)
         groups[KIND_F32] = Group(KIND_F32, g.numerics, segs, off)
         key_segment = dict(plan.key_segment)
         key_segment.update({s.key: s for s in segs})
-        qp = plan.memo["q8plan"] = BucketPlan(plan.keys, groups, plan.key_group, key_segment, plan.n_clients,
+        qp = plan.memo[tag + "plan"] = BucketPlan(plan.keys, groups, plan.key_group, key_segment, plan.n_clients,
                                                 plan.input_kind)
     return qp
 
 
-def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, device):
+def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, device, bits: int = 8):
     """Clients [lo, hi) as one pinned int8 [K, stride] code stack and one fp32 [K, stride / 1024] scale
-    stack on the device; padding is code 0 with scale 0.  Rows are packed in groups (the packer's
-    threads, one row range each) and every group's H2D is queued while the next is packed.  Returns
-    the two device tensors."""
+    stack on the device — for 4-bit codes uint8 [K, stride / 2], a key's packed bytes copied as they
+    are to byte offset / 2, and scales [K, stride / 128]; padding is code 0 with scale 0.  Rows are
+    packed in groups (the packer's threads, one row range each) and every group's H2D is queued while
+    the next is packed.  Returns the two device tensors."""
+    block, _, per_byte, dtype, tag, _ = _LAYOUT[bits]
     k, stride = hi - lo, g32.stride
-    nb = stride // quant.BLOCK
+    nb = stride // block
     pk = agg.packer
-    hq = pk._staging(("q8", slot), (k, stride), torch.int8)
-    hs = pk._staging(("q8s", slot), (k, nb), torch.float32)
+    hq = pk._staging((tag, slot), (k, stride // per_byte), dtype)
+    hs = pk._staging((tag + "s", slot), (k, nb), torch.float32)
     nq, ns = hq.numpy(), hs.numpy()
-    segs = [(s.key, s.offset, s.numel, s.offset // quant.BLOCK, quant.n_blocks(s.numel),
-             s.offset + padded_span(s.numel, quant.BLOCK)) for s in g32.segments]
-    dense = all(b * quant.BLOCK == end - off for _, off, _, _, b, end in segs)  # no empty key: the scales are one run
+    segs = [(s.key, s.offset, s.numel, s.offset // block, quant.n_blocks(s.numel, block),
+             s.offset + padded_span(s.numel, block)) for s in g32.segments]
+    # no empty key and no padding at the row's end: the scales are one run
+    dense = all(b * block == end - off for _, off, _, _, b, end in segs) and sum(b for _, _, _, _, b, _ in segs) == nb
     # a staging buffer last written under this layout keeps its padding (only key bodies are rewritten)
     sig = (tuple((off, numel) for _, off, numel, _, _, _ in segs), k, stride)
     clean = pk.__dict__.setdefault("_q8_clean", {})
-    if clean.get(slot) != sig:
+    if clean.get((tag, slot)) != sig:
         nq[...] = 0
         ns[...] = 0
-        clean[slot] = sig
+        clean[(tag, slot)] = sig
 
     def rows(r0, r1):
         for r in range(r0, r1):
             e, row = entries[lo + r], nq[r]
             for key, off, numel, b0, b, end in segs:
-                row[off : off + numel] = e[key][0].reshape(-1)
+                row[off // per_byte : (off + numel + per_byte - 1) // per_byte] = e[key][0].reshape(-1)
             if dense:
                 ns[r] = scales[lo + r]
             else:
                 for key, off, numel, b0, b, end in segs:
                     ns[r, b0 : b0 + b] = e[key][1]
 
-    dq = pk.device_bucket(("q8", slot), (k, stride), torch.int8, device)
-    ds = pk.device_bucket(("q8s", slot), (k, nb), torch.float32, device)
-    threaded = k > 1 and pk.workers > 1 and k * stride >= SMALL_BYTES
+    dq = pk.device_bucket((tag, slot), (k, stride // per_byte), dtype, device)
+    ds = pk.device_bucket((tag + "s", slot), (k, nb), torch.float32, device)
+    threaded = k > 1 and pk.workers > 1 and k * stride // per_byte >= SMALL_BYTES
     group = 2 * pk.workers if threaded else k
     for g0 in range(0, k, group):
         g1 = min(k, g0 + group)
@@ -109,15 +122,19 @@ def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, d
             rows(g0, g1)
         dq[g0:g1].copy_(hq[g0:g1], non_blocking=True)
     ds.copy_(hs, non_blocking=True)
-    pk._staging_used(("q8", slot), device)
-    pk._staging_used(("q8s", slot), device)
+    pk._staging_used((tag, slot), device)
+    pk._staging_used((tag + "s", slot), device)
     return dq, ds
 
 
 def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_opt: ServerOptimizer | None = None,
                        center=None):
-    """The weighted mean of int8 block-quantized uploads (quant.py's format; FedPAQ, Reisizadeh et al.
-    2020), bit-identical to ensemble(agg_weight_lst, the dequantized uploads, key_lst, server_opt).
+    """The weighted mean of int8 or int4 block-quantized uploads (quant.py's formats; FedPAQ,
+    Reisizadeh et al. 2020), bit-identical to ensemble(agg_weight_lst, the dequantized uploads, key_lst,
+    server_opt).  What follows describes the int8 round; a round of 4-bit uploads (routed on what the
+    uploads hold) is the same with segments on 128-column boundaries, a stride that is a multiple of
+    2048 columns, a uint8 [N, stride / 2] stack, scales [N, stride / 128] and ops.deq_fold_q4_stack,
+    and its audit carries "bits": 4 (an int8 round's audit is as it was: last_quant.get("bits", 8)).
 
     The round is planned with the plan's own numerics (make_plan over zero-strided fp32 stand-ins of
     the quantized keys), its fp32 group re-laid with segments on 1024-column boundaries; the codes are
@@ -143,7 +160,7 @@ def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_op
     if len(w_local_lst) == 0 or len(agg_weight_lst) == 0 or len(agg_weight_lst) != len(w_local_lst):
         make_plan(agg_weight_lst, w_local_lst, key_lst)  # raises what `ensemble` raises
     keys = select_keys(w_local_lst, key_lst)
-    qkeys, delta, entries, scales = quant.check_round(w_local_lst, keys)
+    qkeys, delta, entries, scales, bits = quant.check_round(w_local_lst, keys)
     if not qkeys:
         agg.last_quant = None
         return agg.ensemble(agg_weight_lst, w_local_lst, key_lst, server_opt)
@@ -154,7 +171,8 @@ def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_op
     if nm.mode == na.MODE_W64:
         raise TypeError("a quantized round sums in fp32: weights whose products are float64 (np.float64 / numpy "
                         "integer agg_weight) are not supported — use Python or np.float32 weights")
-    plan = _q8_plan(base)
+    plan = _q_plan(base, bits)
+    block, _, per_byte, _, _, deq_fold = _LAYOUT[bits]
     g32 = plan.groups[KIND_F32]
     if delta and center is None:
         raise ValueError("delta uploads need the server's previous model: no centre was given")
@@ -173,12 +191,12 @@ def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_op
         acc = packer.device_bucket(("acc", KIND_F32), (g32.stride,), torch.float32, device)
         for j, lo in enumerate(range(0, n, k)):
             hi = min(n, lo + k)
-            dq, ds = _pack_chunk(agg, g32, entries, scales, lo, hi, j % 2, device)
+            dq, ds = _pack_chunk(agg, g32, entries, scales, lo, hi, j % 2, device, bits)
             # the whole stride in one launch: padding columns hold sums nobody reads
-            ops.deq_fold_stack(dq, ds, weights[lo:hi], acc if lo else None, acc, center=row, n_clients=hi - lo)
-    nb = g32.stride // quant.BLOCK
-    agg.last_quant = {"bytes_in": n * g32.stride + 4 * n * nb, "bytes_fp32": 4 * n * base.groups[KIND_F32].stride,
-                      "delta": delta, "blocks": n * nb}
+            deq_fold(dq, ds, weights[lo:hi], acc if lo else None, acc, center=row, n_clients=hi - lo)
+    nb = g32.stride // block
+    agg.last_quant = {"bytes_in": n * g32.stride // per_byte + 4 * n * nb, "bytes_fp32": 4 * n * base.groups[KIND_F32].stride,
+                      "delta": delta, "blocks": n * nb, **({"bits": 4} if bits == 4 else {})}
     sums = {KIND_F32: [(packer.shards(plan, KIND_F32)[0], ops.FoldedSum(acc, na.ACC_F32, n, g32.stride))]}
     for kind, parts in stacks8.items():
         sums[kind] = parts

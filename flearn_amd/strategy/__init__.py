@@ -2,7 +2,7 @@
 
 In scope (server reduce on the MI355X engine): AVG, AVGM, OPT, SGD, Prox, BN, LG, LG_R, Dyn,
 Distill; and, beyond the reference, the robust rules TrimmedMean, Median, Krum, MultiKrum and
-NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 block-quantized uploads).  Out of scope (server-side model training): DF, MD, PAV — not
+NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 or int4 block-quantized uploads).  Out of scope (server-side model training): DF, MD, PAV — not
 provided; keep using flearn's for those.
 """
 from .avg import AVG

@@ -1,4 +1,4 @@
-"""FedAVG over int8 block-quantized uploads (quant.py, quantround.py)."""
+"""FedAVG over int8 or int4 block-quantized uploads (quant.py, quantround.py; DESIGN.md sections 17, 18)."""
 from __future__ import annotations
 
 import numpy as np
@@ -36,11 +36,16 @@ class QuantizedAVG(AVG):
     (Alistarh et al. 2017), from numpy.random.default_rng(seed).  server_opt: a ServerOptimizer fused
     into the divide.  A round of plain (unquantized) uploads takes AVG's path unchanged; a round
     mixing the two is refused.  One device; chunk_clients=K folds a quantized round in chunks of K
-    clients.  Client-data errors take server_exception's route."""
+    clients.  Client-data errors take server_exception's route.  bits=4 (`setup_strategy("avg_q4")`):
+    clients upload 4-bit codes, two per byte, with one scale per 128 (an eighth of the fp32 bytes); the
+    server routes on what the uploads hold."""
 
     def __init__(self, server_opt=None, delta=True, stochastic=False, seed=None, encrypt=None, output="reference",
-                 device=None, chunk_clients=None):
+                 device=None, chunk_clients=None, bits=8):
+        if isinstance(bits, bool) or bits not in (8, 4):
+            raise ValueError(f"bits must be 8 or 4, got {bits!r}")
         super().__init__(encrypt, output, device, None, None, chunk_clients)
+        self.bits = int(bits)
         self.server_opt = server_opt
         self.delta = bool(delta)
         self.stochastic = bool(stochastic)
@@ -59,7 +64,7 @@ class QuantizedAVG(AVG):
         """Upload the state_dict quantized: against the last received w_glob when delta is on and
         there is one, else as it is."""
         center = self._received if self.delta else None
-        params = quant.quantize_state_dict(convert_to_np(trainer.weight), center, self.stochastic, self._rng)
+        params = quant.quantize_state_dict(convert_to_np(trainer.weight), center, self.stochastic, self._rng, self.bits)
         return {"agg_weight": agg_weight, "params": params}
 
     def client_receive(self, trainer, server_p_bytes):

@@ -24,7 +24,7 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median),
     f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
     server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
-    server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8")."""
+    server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes)."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -58,6 +58,9 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "avg_q8": lambda: QuantizedAVG(
             strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False),
             strategy_p.get("seed"), **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}),
+        "avg_q4": lambda: QuantizedAVG(
+            strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False),
+            strategy_p.get("seed"), **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}, bits=4),
     }
     if name in factories:
         return factories[name]()

@@ -10,14 +10,15 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 # the device units, one per entry group (each includes only the kernel families it launches)
-SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport", "fa_gram", "fa_clip", "fa_noise", "fa_quant", "fa_quant4")]
+SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport", "fa_gram", "fa_clip", "fa_noise", "fa_quant", "fa_quant4", "fa_trimwide")]
 # flags of single units, after the common ones.  fa_quant4 is built with packed fp32 operations off (cc1's target
 # feature, cleared): the build that ships is the one that was run, tested and measured.  The packed build of the same
 # source has only been compiled: it was never run, so it is neither checked against the unit's bit-exact tests nor
 # timed (DESIGN.md section 18 gives both instruction counts, 4.41 against 2.9 VALU per element, and
 # profiles/quant4/resource_usage.txt both resource rows).  Removing this entry is the whole switch to the packed
 # build; the kernel source needs nothing, and the grid rule is to be measured again with it.
-UNIT_FLAGS = {"fa_quant4": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+UNIT_FLAGS = {"fa_quant4": _NO_PACKED_FP32, "fa_trimwide": _NO_PACKED_FP32}  # fa_trimwide: integer keys and one fp32 chain
 HOST_SOURCES = [HERE / "csrc" / "fa_wire.cpp"]  # plain host C++ (g++), linked into the same .so
 DEPS = sorted((HERE / "csrc").glob("*.hpp"))  # every header: a new one cannot be forgotten
 MAX_COMPILE_JOBS = 8

@@ -3,7 +3,7 @@
 // segmented reduce of fa_segrows.hpp over them, fa_gather_rows* copy per-client tensors into a
 // stack), the streamed rounds (fa_fold / fa_fold_finish, fa_fold.hpp), the trimmed sums
 // (fa_trim_sum, fa_trim.hpp: one column per lane, the clients sorted in registers, one instantiation
-// per padded depth, the 8-byte kinds by repeated selection) and the standalone update fa_opt_apply.
+// per padded depth, the 8-byte kinds by repeated selection, for fa_trim_sum_wide too) and the standalone update fa_opt_apply.
 // Host side only, as fa_reduce.hip.  The fold entries share this unit with the segmented reduce on
 // purpose: see the note at launch_fold_rows.
 #include <algorithm>
@@ -164,6 +164,15 @@ int launch_trim_elem(int64_t grid, const void* stack, int64_t stride, int n, int
   return launch_check();
 }
 }  // namespace
+
+// The 8-byte kinds of fa_trim_sum and fa_trim_sum_wide (fa_trimwide.hip, which instantiates no kernel
+// of fa_trim.hpp): trim_kernel_elem is correct for any n_clients
+int fa::host::launch_trim_elem_kind(int acc_kind, const void* stack, int64_t stride, int n, int trim, void* acc_out,
+                                    int64_t col0, int64_t ncols, hipStream_t s) {
+  const int64_t grid = trim_elem_grid(ncols, device_cus(), g_reduce_grid.load(std::memory_order_relaxed));
+  if (acc_kind == FA_ACC_F64) return launch_trim_elem<double>(grid, stack, stride, n, trim, acc_out, col0, ncols, s);
+  return launch_trim_elem<int64_t>(grid, stack, stride, n, trim, acc_out, col0, ncols, s);
+}
 
 extern "C" {
 
@@ -400,10 +409,7 @@ int fa_trim_sum(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t
   if (acc_kind == FA_ACC_F32)
     return launch_trim_rows(plan_trim_window(n_clients, n_cols, device_cus(), forced), static_cast<const float*>(stack),
                             row_stride, n_clients, trim, static_cast<float*>(acc_out), col_begin, n_cols, s);
-  const int64_t grid = trim_elem_grid(n_cols, device_cus(), forced);
-  if (acc_kind == FA_ACC_F64)
-    return launch_trim_elem<double>(grid, stack, row_stride, n_clients, trim, acc_out, col_begin, n_cols, s);
-  return launch_trim_elem<int64_t>(grid, stack, row_stride, n_clients, trim, acc_out, col_begin, n_cols, s);
+  return launch_trim_elem_kind(acc_kind, stack, row_stride, n_clients, trim, acc_out, col_begin, n_cols, s);
 }
 
 }  // extern "C"

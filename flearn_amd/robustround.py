@@ -38,12 +38,12 @@ def _refuse(agg, server_opt) -> None:
         raise TypeError("FedDyn's h update needs the plain sum over all clients: no robust round with Dyn state")
 
 
-def _plan_unit_weights(w_local_lst, key_lst, max_clients: int, what: str) -> BucketPlan:
+def _plan_unit_weights(w_local_lst, key_lst, max_clients: int, what: str, hint: str = "") -> BucketPlan:
     """make_plan's plan for Python-int weights of 1 (key intersection, layouts and errors as in
     `ensemble`), for at most max_clients uploads and no float16 bucket."""
     n = len(w_local_lst)
     if n > max_clients:
-        raise ValueError(f"a {what} round takes at most {max_clients} clients, got {n}")
+        raise ValueError(f"a {what} round takes at most {max_clients} clients, got {n}{hint}")
     plan = make_plan([1] * n, w_local_lst, key_lst)
     if KIND_F16 in plan.groups:
         raise TypeError("float16 uploads: a robust round aggregates fp32 / float64 / int64 buckets only")
@@ -51,7 +51,8 @@ def _plan_unit_weights(w_local_lst, key_lst, max_clients: int, what: str) -> Buc
 
 
 # -- coordinate-wise trimmed mean and median ---------------------------------------------------
-def ensemble_trimmed(agg, w_local_lst, trim: int, key_lst=None, server_opt: ServerOptimizer | None = None):
+def ensemble_trimmed(agg, w_local_lst, trim: int, key_lst=None, server_opt: ServerOptimizer | None = None,
+                     wide: bool = False):
     """The coordinate-wise trimmed mean of the uploads (Yin et al., ICML 2018): per element, the
     N clients' values in IEEE totalOrder, the `trim` smallest and the `trim` largest dropped, the
     rest summed in ascending order in the bucket's sum type and divided by N - 2 * trim (the
@@ -65,9 +66,17 @@ def ensemble_trimmed(agg, w_local_lst, trim: int, key_lst=None, server_opt: Serv
     Refused before anything is queued: float16 buckets and FedDyn state (TypeError: its h
     update needs the plain sum over all N); several devices, group= and chunk_clients
     (ValueError: every client must be present for a column's order statistics); more than
-    128 clients and a trim outside 0 <= 2 * trim < N (ValueError)."""
+    128 clients and a trim outside 0 <= 2 * trim < N (ValueError).
+
+    wide=True takes up to 1024 clients (fa_trim_sum_wide: past 128 a column's clients are sorted
+    across lanes through LDS; float64 / int64 buckets by repeated selection, O(N^2) per element,
+    meant for small buffers such as BN counters).  Everything else is the same round."""
     _refuse(agg, server_opt)
-    plan = _plan_unit_weights(w_local_lst, key_lst, na.TRIM_MAX_CLIENTS, "robust")
+    if wide:
+        plan = _plan_unit_weights(w_local_lst, key_lst, na.TRIM_WIDE_MAX_CLIENTS, "robust")
+    else:
+        plan = _plan_unit_weights(w_local_lst, key_lst, na.TRIM_MAX_CLIENTS, "robust",
+                                  f" (wide=True takes {na.TRIM_WIDE_MAX_CLIENTS})")
     n = plan.n_clients
     if isinstance(trim, bool) or not isinstance(trim, (int, np.integer)) or trim < 0 or 2 * trim >= n:
         raise ValueError(f"trim must be an integer with 0 <= 2 * trim < {n} clients, got {trim!r}")
@@ -86,7 +95,7 @@ def ensemble_trimmed(agg, w_local_lst, trim: int, key_lst=None, server_opt: Serv
         with torch.cuda.device(sh.device):
             ak = ops.acc_kind_of(kind, g.numerics.mode)
             acc = packer.device_bucket(("acc", kind), (g.stride,), ops._ACC_TORCH[ak], sh.device)
-            ops.trim_sum_stack(ak, stack, trim, acc, n_clients=n)
+            ops.trim_sum_stack(ak, stack, trim, acc, n_clients=n, wide=wide)
             packer.hold_slab(kind, [stack], sh.device)
         sums[kind] = [(sh, ops.FoldedSum(acc, ak, n, sh.width))]
     return agg._finish(plan, agg._server_step(plan, sums, server_opt))

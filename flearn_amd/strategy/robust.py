@@ -43,14 +43,16 @@ class TrimmedMean(_RobustRound):
     round).  trim = 0 is a mean summed in sorted order, not FedAVG's list-order sum.
     server_opt: a ServerOptimizer (AVGM / Adagrad / Yogi / Adam) fused into the round's divide,
     with w_local := the previous global model, as AVGM / OPT(server_side=True) do.
-    At most 128 clients per round, one device, fp32 / float64 / int64 tensors; anything else takes
-    server_exception's route, like any client-data error.  `agg_weight` is required and ignored."""
+    At most 128 clients per round (wide=True: 1024, Aggregator.ensemble_trimmed), one device, fp32 /
+    float64 / int64 tensors; anything else takes server_exception's route, like any client-data error.
+    `agg_weight` is required and ignored."""
 
     def __init__(self, trim=0.1, server_opt=None, encrypt=None, output="reference", device=None, devices=None,
-                 group=None, chunk_clients=None):
+                 group=None, chunk_clients=None, wide=False):
         super().__init__(encrypt, output, device, devices, group, chunk_clients)
         self.trim = self._check_trim(trim)
         self.server_opt = server_opt
+        self.wide = bool(wide)
 
     @staticmethod
     def _check_trim(trim):
@@ -75,16 +77,18 @@ class TrimmedMean(_RobustRound):
     def server_ensemble(self, agg_weight_lst, w_local_lst, key_lst=None, server_opt=None):
         """The engine's robust round (Aggregator.ensemble_trimmed).  agg_weight_lst is checked for
         presence by server_pre_processing and not used."""
-        return self.engine.ensemble_trimmed(w_local_lst, self.trim_count(len(w_local_lst)), key_lst, server_opt=server_opt)
+        return self.engine.ensemble_trimmed(w_local_lst, self.trim_count(len(w_local_lst)), key_lst, server_opt=server_opt,
+                                            wide=self.wide)
 
 
 class Median(TrimmedMean):
     """Coordinate-wise median: the trimmed mean with t = (N - 1) // 2, which keeps one value for
-    odd N and the mean of the two middle values for even N.  `agg_weight` is required and ignored."""
+    odd N and the mean of the two middle values for even N.  wide=True: up to 1024 clients, as for
+    TrimmedMean.  `agg_weight` is required and ignored."""
 
     def __init__(self, server_opt=None, encrypt=None, output="reference", device=None, devices=None, group=None,
-                 chunk_clients=None):
-        super().__init__(0, server_opt, encrypt, output, device, devices, group, chunk_clients)
+                 chunk_clients=None, wide=False):
+        super().__init__(0, server_opt, encrypt, output, device, devices, group, chunk_clients, wide)
 
     def trim_count(self, n_clients: int) -> int:
         return max(0, (n_clients - 1) // 2)

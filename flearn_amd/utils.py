@@ -21,7 +21,7 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     """Name -> strategy instance, as common/utils.py:16-58.  Unknown names fall back to
     `custom_strategy`, else SystemError.  Extra keyword arguments understood here:
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
-    (engine), server_side (AVGM / OPT), trim and server_opt (TrimmedMean; server_opt also Median),
+    (engine), server_side (AVGM / OPT), trim, server_opt and wide (TrimmedMean; Median: all but trim),
     f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
     server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
     server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes)."""
@@ -41,8 +41,9 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "opt": lambda: OPT(server_side=server_side, **eng),
         "sgd": lambda: SGD(**eng),
         "prox": lambda: Prox(**eng),
-        "trimmedmean": lambda: TrimmedMean(strategy_p.get("trim", 0.1), strategy_p.get("server_opt"), **eng),
-        "median": lambda: Median(strategy_p.get("server_opt"), **eng),
+        "trimmedmean": lambda: TrimmedMean(strategy_p.get("trim", 0.1), strategy_p.get("server_opt"), **eng,
+                                             wide=strategy_p.get("wide", False)),
+        "median": lambda: Median(strategy_p.get("server_opt"), **eng, wide=strategy_p.get("wide", False)),
         "krum": lambda: Krum(strategy_p.get("f", 0), strategy_p.get("server_opt"), strategy_p.get("center", "previous"), **eng),
         "multikrum": lambda: MultiKrum(strategy_p.get("f", 0), strategy_p.get("m"), strategy_p.get("server_opt"),
                                        strategy_p.get("center", "previous"), **eng),

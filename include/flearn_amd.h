@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 24
+#define FA_ABI_VERSION 25
 
 /* return codes */
 #define FA_OK 0
@@ -274,7 +274,7 @@ int fa_set_reduce_grid(int32_t grid);
 int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
- * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_gram_f32 / fa_rownorm2_f32 /
+ * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_rownorm2_f32 /
  * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
@@ -355,6 +355,19 @@ int fa_fold_finish(int32_t acc_kind, int32_t mode, const void* acc, double denom
  * fa_last_launch names the instantiation, e.g. "trim_kernel_rows<128,4,true>".               */
 int fa_trim_sum(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients,
                 int32_t trim, void* acc_out, int64_t col_begin, int64_t n_cols, void* stream);
+
+/* fa_trim_sum for up to FA_TRIM_WIDE_MAX_CLIENTS clients: the same sums, arguments and errors, with
+ * this cap in place of FA_TRIM_MAX_CLIENTS.  Opt-in: fa_trim_sum keeps
+ * refusing client 129.  FA_ACC_F32 with n_clients <= FA_TRIM_MAX_CLIENTS is fa_trim_sum's launch,
+ * bit for bit and in fa_last_launch; with 129 <= n_clients <= 1024 a column's clients are sorted by
+ * 2, 4 or 8 lanes (runs of 128 in registers, merged through LDS) and fa_last_launch names
+ * "merge_trim_kernel<NP,true>", NP = 256, 512 or 1024.  FA_ACC_F64 and FA_ACC_I64 take fa_trim_sum's
+ * selection kernel at any depth: O(n_clients^2) loads per column, meant for small buckets such as
+ * BN counters.  Every error is decided before any HIP call.  Nothing outside acc_out[0, n_cols) is
+ * written; n_cols == 0 is a no-op.  fa_set_reduce_grid applies.  ABI 25.                          */
+#define FA_TRIM_WIDE_MAX_CLIENTS 1024
+int fa_trim_sum_wide(int32_t acc_kind, const void* stack, int64_t row_stride, int32_t n_clients,
+                     int32_t trim, void* acc_out, int64_t col_begin, int64_t n_cols, void* stream);
 
 /* ---- robust aggregation: the client Gram matrix (Krum / multi-Krum) -------
  * Blanchard et al. (NeurIPS 2017) judge whole uploads by their squared distances to the others;

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 25
+ABI_VERSION = 26
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -82,6 +82,7 @@ EXPORTS = (
     "fa_gauss_add_f32",
     "fa_deq_fold_q8",
     "fa_deq_fold_q4",
+    "fa_fold_bf16",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -264,6 +265,7 @@ def load(require_gpu: bool = False):
                 "fa_gauss_add_f32": ([P, I64, I64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, P], ctypes.c_int),
                 "fa_deq_fold_q8": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_deq_fold_q4": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
+                "fa_fold_bf16": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

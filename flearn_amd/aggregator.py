@@ -10,7 +10,8 @@ either kind of weighted sum (ops.StackSum, ops.FoldedSum).  The robust rounds, `
 `ensemble_clipped` (norm clipping), are
 robustround.py's, bound on the class; they end in the same server step.  `begin_clipped_round` and
 `ensemble_clipped_chunked` (clipstream.py) run the clipped round in chunks of clients;
-`ensemble_quantized` (quantround.py) sums int8 or int4 block-quantized uploads.
+`ensemble_quantized` (quantround.py) sums int8 or int4 block-quantized uploads,
+`ensemble_bf16` (bf16round.py) bfloat16 uploads.
 
 The device-level entry points on torch CUDA tensors are ops.py, the resident optimizer state
 (`ServerOptimizer`, `DynState`) serverstate.py, the small-host-round fast path smallround.py; every
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as na
-from . import clipstream, quantround, robustround, smallround
+from . import bf16round, clipstream, quantround, robustround, smallround
 from .bucketplan import BucketPlan, Shard, key_runs, make_plan, rank_width, select_keys  # noqa: F401
 from .dist import gather_columns
 from .ops import (FoldedSum, StackSum, _byte_range, _check_arrays, _check_cuda, _check_stack, _check_v_out,  # noqa: F401
@@ -88,6 +89,10 @@ class Aggregator:
     #: 4-bit rounds existed): read the width as last_quant.get("bits", 8)
     ensemble_quantized = quantround.ensemble_quantized
     last_quant = None
+    #: the round of bfloat16 uploads (bf16round.py); last_bf16: its audit.  `ensemble` itself keeps
+    #: refusing bfloat16 tensors
+    ensemble_bf16 = bf16round.ensemble_bf16
+    last_bf16 = None
 
     def __init__(self, device=None, output: str = "reference", workers: int = 8, devices=None, group=None,
                  reorder: bool = False, chunk_clients: int | None = None):

@@ -7,7 +7,8 @@ makes the accumulator of a robust round (per column, the sorted clients' middle 
 the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
 accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise;
 `deq_fold_stack` adds a chunk of int8 block-quantized client rows to an fp32 accumulator and
-`deq_fold_q4_stack` one of int4 rows, two codes per byte.  `StackSum`
+`deq_fold_q4_stack` one of int4 rows, two codes per byte; `fold_bf16_stack` adds a chunk of
+bfloat16 client rows, widened in registers.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
 """
@@ -515,6 +516,41 @@ def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_i
                                   weights.data_ptr(), _ptr(center), _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols,
                                   na.stream_handle(dev))
     na.check(rc, entry)
+
+
+_BF16_STACK_DTYPES = (torch.bfloat16, torch.int16, torch.uint16)
+
+
+def fold_bf16_stack(stack_u16: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *, col_begin: int = 0,
+                    n_cols: int | None = None, n_clients: int | None = None) -> None:
+    """One chunk of bfloat16 client rows added to an fp32 accumulator (fa_fold_bf16; DESIGN.md section
+    20, restated by tests/bf16_ref.py), queued on torch's current stream.  Per column c of the window
+    and row i in list order, every operation rounded to fp32: x = the float whose bits are
+    stack_u16[i, col_begin + c] << 16 (exact); acc_out[c] = acc + weights[i] * x, acc starting from
+    acc_in[c] — or, acc_in None, from row 0's product: the chunk opens the round.  The bits are
+    fold_stack's (na.ACC_F32) on the widened rows, and fold_finish divides the accumulator.
+    stack_u16: [N, stride] bfloat16 bit patterns (torch.bfloat16, int16 or uint16), stride and
+    col_begin multiples of 8; weights: fp32 [>= N].  acc_out may be acc_in.  No client cap."""
+    if (not isinstance(stack_u16, torch.Tensor) or stack_u16.dim() != 2 or stack_u16.stride(1) != 1
+            or not stack_u16.is_cuda):
+        raise ValueError("stack_u16 must be a 2-D device tensor with contiguous rows")
+    if stack_u16.dtype not in _BF16_STACK_DTYPES:
+        raise TypeError(f"stack_u16 must hold bfloat16 bit patterns (torch.bfloat16, int16 or uint16), got {stack_u16.dtype}")
+    n, ncols = _check_window(stack_u16.shape, col_begin, n_cols, n_clients)
+    dev = stack_u16.device
+    if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != dev
+            or not weights.is_contiguous() or weights.numel() < n):
+        raise ValueError(f"weights must be a contiguous torch.float32 tensor of at least {n} elements on the stack's device")
+    for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
+        if name == "acc_in" and t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.numel() < ncols
+                or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous torch.float32 tensor of at least {ncols} elements on the "
+                             "stack's device")
+    rc = na.lib().fa_fold_bf16(stack_u16.data_ptr(), stack_u16.stride(0), n, weights.data_ptr(), _ptr(acc_in),
+                               acc_out.data_ptr(), col_begin, ncols, na.stream_handle(dev))
+    na.check(rc, "fa_fold_bf16")
 
 
 def gauss_add(acc: torch.Tensor, sigma: float, seed: int, sequence: int, *, col_begin: int = 0,

@@ -2,11 +2,12 @@
 
 In scope (server reduce on the MI355X engine): AVG, AVGM, OPT, SGD, Prox, BN, LG, LG_R, Dyn,
 Distill; and, beyond the reference, the robust rules TrimmedMean, Median, Krum, MultiKrum and
-NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 or int4 block-quantized uploads).  Out of scope (server-side model training): DF, MD, PAV — not
+NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 or int4 block-quantized uploads) and BF16AVG (bf16.py: bfloat16 uploads).  Out of scope (server-side model training): DF, MD, PAV — not
 provided; keep using flearn's for those.
 """
 from .avg import AVG
 from .avgm import AVGM
+from .bf16 import BF16AVG
 from .bn import BN
 from .distill import Distill
 from .dyn import Dyn
@@ -38,6 +39,7 @@ __all__ = [
     "NormClip",
     "StreamedNormClip",
     "QuantizedAVG",
+    "BF16AVG",
     "ParentStrategy",
     "Strategy",
     "BaseEncrypt",

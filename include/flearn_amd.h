@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 25
+#define FA_ABI_VERSION 26
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -552,6 +552,29 @@ int fa_deq_fold_q4(const uint8_t* stack, int64_t row_stride, int32_t n_clients, 
                    int64_t scale_stride, const float* weights, const float* center,
                    const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
                    void* stream);
+
+/* ---- bfloat16 uploads (ABI 26) --------------------------------------------
+ * A bfloat16 client row is one 16-bit pattern per column: the high half of the fp32 of the same
+ * value.  There is no reference counterpart.  fa_fold_bf16 adds one chunk of n_clients such rows to
+ * an fp32 accumulator without widening them in memory.  Per column c of the window and row i, every
+ * operation rounded to fp32 and none contracted:
+ *   x   = the float whose bits are (uint32_t)stack[i * row_stride + col_begin + c] << 16    (exact)
+ *   acc = fl32(acc + fl32(weights[i] * x))                     in list order
+ * acc starts from acc_in[c]; acc_in == NULL opens the round: acc = fl32(weights[0] * x_0), the other
+ * rows added.  These are fa_fold's (FA_ACC_F32) bits on the widened rows for every input: an all
+ * -0.0 column, bfloat16 subnormals (fp32 subnormals: kept), +-inf and sums that overflow included;
+ * only a NaN's bits are free.  row_stride is in elements (2 bytes each); acc_in / acc_out are
+ * indexed from 0 at col_begin.  acc_out may be acc_in.  Weights are read from device memory per row:
+ * no client cap.
+ * FA_ERR_ARG: a NULL stack / weights / acc_out, n_clients < 1, n_cols < 0, a window outside the
+ * row, or acc_in overlapping acc_out within n_cols elements without equalling it.  FA_ERR_ALIGN:
+ * stack / acc_in / acc_out not 16-byte aligned, row_stride or col_begin no multiple of 8, weights not
+ * 4-byte aligned.  Every error is decided before any HIP call.  n_cols == 0 is a no-op that launches
+ * nothing.  Rows are read through a range rounded up to a dword (inside the row); nothing outside
+ * acc_out[0, n_cols) is written.  fa_set_reduce_grid applies; fa_last_launch names the
+ * instantiation, e.g. "widen_fold_kernel<4,4,4,true>", launches = 1.                              */
+int fa_fold_bf16(const uint16_t* stack, int64_t row_stride, int32_t n_clients, const float* weights,
+                 const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

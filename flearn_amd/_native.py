@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 26
+ABI_VERSION = 27
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -35,6 +35,7 @@ TRIM_WIDE_MAX_CLIENTS = 1024  # fa_trim_sum_wide's (FA_TRIM_WIDE_MAX_CLIENTS)
 GRAM_MAX_CLIENTS = 128  # fa_gram_f32's (FA_GRAM_MAX_CLIENTS)
 Q8_BLOCK = 1024  # columns per scale of a quantized row (FA_Q8_BLOCK)
 Q4_BLOCK, Q4_CHUNK = 128, 2048  # of a 4-bit quantized row, and fa_deq_fold_q4's col_begin unit (FA_Q4_BLOCK, FA_Q4_CHUNK)
+Q1_BLOCK, Q1_CHUNK = 128, 2048  # of a 1-bit sign row, and fa_deq_fold_q1's col_begin unit (FA_Q1_BLOCK, FA_Q1_CHUNK)
 CLIP_MAX_CLIENTS = 128  # fa_rownorm2_f32's and fa_clip_sum_f32's (FA_CLIP_MAX_CLIENTS)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
@@ -83,6 +84,7 @@ EXPORTS = (
     "fa_deq_fold_q8",
     "fa_deq_fold_q4",
     "fa_fold_bf16",
+    "fa_deq_fold_q1",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -266,6 +268,7 @@ def load(require_gpu: bool = False):
                 "fa_deq_fold_q8": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_deq_fold_q4": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_fold_bf16": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
+                "fa_deq_fold_q1": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

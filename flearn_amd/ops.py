@@ -7,7 +7,8 @@ makes the accumulator of a robust round (per column, the sorted clients' middle 
 the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
 accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise;
 `deq_fold_stack` adds a chunk of int8 block-quantized client rows to an fp32 accumulator and
-`deq_fold_q4_stack` one of int4 rows, two codes per byte; `fold_bf16_stack` adds a chunk of
+`deq_fold_q4_stack` one of int4 rows, two codes per byte, `deq_fold_q1_stack` one of sign rows, eight
+bits per byte with a magnitude per 128; `fold_bf16_stack` adds a chunk of
 bfloat16 client rows, widened in registers.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
 `mean(...)` with reduce_stack's keyword names, so the engine's server step is written once.
@@ -485,8 +486,22 @@ def deq_fold_q4_stack(stack_u8: torch.Tensor, scales: torch.Tensor, weights: tor
               col_begin, n_cols, n_clients)
 
 
+def deq_fold_q1_stack(stack_u8: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+                      center: torch.Tensor | None = None, n_clients: int | None = None, col_begin: int = 0,
+                      n_cols: int | None = None) -> None:
+    """deq_fold_stack for 1-bit sign rows (fa_deq_fold_q1; DESIGN.md section 21, restated by
+    tests/quant1_ref.py).  stack_u8: uint8 [N, stride bytes], stride a multiple of 16, holding
+    8 * stride columns per row: column c is bit c % 8 of byte c // 8, 1 = negative.  Columns (col_begin,
+    n_cols, the centre's and the accumulators' indices) are elements.  x = the scale
+    scales[i, (col_begin + c) // 128] with the bit's sign (a bit pattern, no product), the rest as
+    deq_fold_stack; scales: fp32 [N, >= ceil((col_begin + n_cols) / 128)], finite and >= 0; col_begin
+    a multiple of 2048.  The bits are fold_stack's (na.ACC_F32) on the dequantized rows."""
+    _deq_fold("fa_deq_fold_q1", "stack_u8", torch.uint8, 8, na.Q1_BLOCK, stack_u8, scales, weights, acc_in, acc_out, center,
+              col_begin, n_cols, n_clients)
+
+
 def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_in, acc_out, center, col_begin, n_cols, n_clients):
-    """The checks and the call deq_fold_stack and deq_fold_q4_stack share: `stack` holds `per_byte`
+    """The checks and the call deq_fold_stack, deq_fold_q4_stack and deq_fold_q1_stack share: `stack` holds `per_byte`
     columns per byte and one scale per `block` columns."""
     if (not isinstance(stack, torch.Tensor) or stack.dim() != 2 or stack.stride(1) != 1
             or not stack.is_cuda):

@@ -1,5 +1,5 @@
-"""Int8 and int4 block-quantized uploads (DESIGN.md sections 17 and 18): the formats, their checks,
-and the client's quantizer and dequantizer.  Host-side numpy only, no device code.
+"""Int8, int4 and 1-bit sign block-quantized uploads (DESIGN.md sections 17, 18 and 21): the formats,
+their checks, and the client's quantizer and dequantizer.  Host-side numpy only, no device code.
 
 A quantized entry of upload["params"] replaces an fp32 tensor of shape S by a plain dict
 
@@ -24,6 +24,19 @@ quantizer leaves an odd tensor's spare high nibble 0; on receipt that nibble is 
 holds (it is no element: dequantize_entry drops it, and on the device it lands in a padding column
 nobody reads).  One round's uploads are all of one width.
 
+The 1-bit entry (bits=1) is a sign per element and a magnitude per block of 128 (scaled signSGD;
+EF-signSGD, Karimireddy et al., ICML 2019):
+
+    {"q1": uint8 ndarray [ceil(numel / 8)], "shape": tuple S, "scale": float32 ndarray [ceil(numel / 128)],
+     "block": 128, "delta": bool}
+
+Element e (C order) is bit e % 8 of byte e >> 3; 1 is negative, 0 non-negative (exact zeros, -0.0 and
+the last byte's spare bits are 0).  scale[b] is the mean of |x| over the block's real elements,
+accumulated in float64 and rounded once to fp32; a legal scale is finite and >= 0.  The value is
+copysign(scale[b], -1 if bit else +1) — a bit pattern, not a product — plus the centre for a delta
+entry.  A sign code has no zero: the quantizer is biased, and a client keeps the residual
+(QuantizedAVG's error_feedback).  Spare bits are ignored on receipt, as q4's spare nibble is.
+
 Block-wise absmax scaling as in Dettmers et al. (ICLR 2022); quantized client updates as in FedPAQ
 (Reisizadeh et al., AISTATS 2020); the stochastic rounding is QSGD's (Alistarh et al., NeurIPS 2017).
 """
@@ -37,9 +50,12 @@ import torch
 BLOCK = 1024  # FA_Q8_BLOCK: one wave-chunk of fa_deq_fold_q8
 Q4_BLOCK = 128  # FA_Q4_BLOCK: a sixteenth of fa_deq_fold_q4's wave-chunk
 Q4_MIN_SCALE = np.float32(2.0 ** -100)  # FA_Q4_MIN_SCALE: the smallest non-zero scale of a 4-bit entry
+Q1_BLOCK = 128  # FA_Q1_BLOCK: a sixteenth of fa_deq_fold_q1's wave-chunk
 _F32 = np.dtype(np.float32)
-_BLOCK_OF = {8: BLOCK, 4: Q4_BLOCK}
-_LEVELS = {8: 127, 4: 7}
+_BLOCK_OF = {8: BLOCK, 4: Q4_BLOCK, 1: Q1_BLOCK}
+_LEVELS = {8: 127, 4: 7, 1: 1}
+_PACKED = {4: ("q4", 2), 1: ("q1", 8)}  # the widths whose codes are packed bytes: (field, codes per byte)
+_BITS_MSG = "bits must be 8, 4 or 1"
 
 
 def n_blocks(numel: int, block: int = BLOCK) -> int:
@@ -47,18 +63,18 @@ def n_blocks(numel: int, block: int = BLOCK) -> int:
 
 
 def is_entry(v) -> bool:
-    """v is (shaped like) a quantized entry: a dict with a "q8" or a "q4"."""
-    return isinstance(v, dict) and ("q8" in v or "q4" in v)
+    """v is (shaped like) a quantized entry: a dict with a "q8", a "q4" or a "q1"."""
+    return isinstance(v, dict) and ("q8" in v or "q4" in v or "q1" in v)
 
 
 def bits_of(e) -> int:
     """The code width of a quantized entry."""
-    return 4 if "q4" in e else 8
+    return 4 if "q4" in e else 1 if "q1" in e else 8
 
 
 def entry_shape(e) -> tuple:
     """The shape of the tensor an entry stands for."""
-    return tuple(e["shape"]) if "q4" in e else tuple(e["q8"].shape)
+    return tuple(e["shape"]) if "q4" in e or "q1" in e else tuple(e["q8"].shape)
 
 
 def pack_nibbles(codes: np.ndarray) -> np.ndarray:
@@ -76,6 +92,17 @@ def unpack_nibbles(q4: np.ndarray, numel: int) -> np.ndarray:
     out[0::2] = (q4 << 4).view(np.int8) >> 4
     out[1::2] = q4.view(np.int8) >> 4
     return out[:numel]
+
+
+def pack_signs(neg: np.ndarray) -> np.ndarray:
+    """A flat bool array (True = negative) as uint8 [ceil(n / 8)]: element e in bit e % 8 of byte e >> 3,
+    the last byte's spare bits 0."""
+    return np.packbits(neg, bitorder="little")
+
+
+def unpack_signs(q1: np.ndarray, numel: int) -> np.ndarray:
+    """pack_signs' inverse: the first `numel` bits of a uint8 array, as bool."""
+    return np.unpackbits(q1, count=numel, bitorder="little").astype(bool)
 
 
 def is_quantized(params) -> bool:
@@ -101,6 +128,8 @@ def check_entry(key, e, client=None):
     where = f"key {key!r}" if client is None else f"client {client} key {key!r}"
     if "q4" in e:
         return _check_entry4(where, e)
+    if "q1" in e:
+        return _check_entry4(where, e, 1)
     for f in ("q8", "scale", "block", "delta"):
         if f not in e:
             raise ValueError(f"{where}: quantized entry lacks {f!r}")
@@ -121,18 +150,21 @@ def check_entry(key, e, client=None):
     return np.ascontiguousarray(q8), np.ascontiguousarray(scale), bool(e["delta"])
 
 
-def _check_entry4(where: str, e):
-    """check_entry for a 4-bit entry: (q4 as a C-contiguous uint8 array, scale, delta).  Beyond q8's
-    refusals: a missing or malformed shape and a code count other than ceil(numel / 2) (ValueError), a
-    q4 that is no uint8 array (TypeError), a scale in (0, Q4_MIN_SCALE) (ValueError).  An odd tensor's
-    spare high nibble is not looked at."""
-    for f in ("q4", "shape", "scale", "block", "delta"):
+def _check_entry4(where: str, e, bits: int = 4):
+    """check_entry for an entry of packed codes, 4-bit or (bits=1) 1-bit: (the code bytes as a
+    C-contiguous uint8 array, scale, delta).  Beyond q8's refusals: a missing or malformed shape and a
+    code count other than ceil(numel / 2) — 1-bit: ceil(numel / 8) — (ValueError), codes that are no
+    uint8 array (TypeError), codes of two widths in one entry, and for 4 bits a scale in
+    (0, Q4_MIN_SCALE) (ValueError).  A last byte's spare nibble or bits are not looked at."""
+    tag, per = _PACKED[bits]
+    for f in (tag, "shape", "scale", "block", "delta"):
         if f not in e:
             raise ValueError(f"{where}: quantized entry lacks {f!r}")
-    if "q8" in e:
-        raise ValueError(f"{where}: an entry carries q4 or q8 codes, not both")
-    if isinstance(e["block"], bool) or not isinstance(e["block"], (int, np.integer)) or int(e["block"]) != Q4_BLOCK:
-        raise ValueError(f"{where}: block must be {Q4_BLOCK} for 4-bit codes, got {e['block']!r}")
+    if sum(t in e for t in ("q8", "q4", "q1")) > 1:
+        raise ValueError(f"{where}: an entry carries q4 or q8 codes, not both" if "q1" not in e else
+                         f"{where}: an entry carries codes of one width, not both q1 and another")
+    if isinstance(e["block"], bool) or not isinstance(e["block"], (int, np.integer)) or int(e["block"]) != _BLOCK_OF[bits]:
+        raise ValueError(f"{where}: block must be {_BLOCK_OF[bits]} for {bits}-bit codes, got {e['block']!r}")
     if not isinstance(e["delta"], (bool, np.bool_)):
         raise ValueError(f"{where}: delta must be a bool, got {e['delta']!r}")
     shape = e["shape"]
@@ -140,25 +172,26 @@ def _check_entry4(where: str, e):
             isinstance(d, (int, np.integer)) and not isinstance(d, bool) and d >= 0 for d in shape):
         raise ValueError(f"{where}: shape must be a tuple of non-negative ints, got {shape!r}")
     numel = int(np.prod(shape, dtype=np.int64))
-    q4 = _host_array(e["q4"], f"{where} q4")
+    q4 = _host_array(e[tag], f"{where} {tag}")
     if q4.dtype != np.uint8:
-        raise TypeError(f"{where}: q4 must be uint8 (two codes per byte), got {q4.dtype}")
-    if q4.ndim != 1 or q4.shape[0] != (numel + 1) // 2:
-        raise ValueError(f"{where}: {numel} elements need {(numel + 1) // 2} code bytes, got shape {tuple(q4.shape)}")
+        raise TypeError(f"{where}: {tag} must be uint8 ({'two' if bits == 4 else 'eight'} codes per byte), got {q4.dtype}")
+    if q4.ndim != 1 or q4.shape[0] != (numel + per - 1) // per:
+        raise ValueError(f"{where}: {numel} elements need {(numel + per - 1) // per} code bytes, got shape {tuple(q4.shape)}")
     scale = _host_array(e["scale"], f"{where} scale")
     if scale.dtype != _F32:
         raise TypeError(f"{where}: scale must be float32, got {scale.dtype}")
     if scale.ndim != 1 or scale.shape[0] != n_blocks(numel, Q4_BLOCK):
         raise ValueError(f"{where}: {numel} elements need {n_blocks(numel, Q4_BLOCK)} scales, got shape {tuple(scale.shape)}")
-    if not _scales_ok(scale, 4):
-        raise ValueError(f"{where}: 4-bit scales must be finite and either 0 or >= 2^-100")
+    if not _scales_ok(scale, bits):
+        raise ValueError(f"{where}: 4-bit scales must be finite and either 0 or >= 2^-100" if bits == 4 else
+                         f"{where}: 1-bit scales must be finite and >= 0")
     return np.ascontiguousarray(q4), np.ascontiguousarray(scale), bool(e["delta"])
 
 
 def _scales_ok(scale: np.ndarray, bits: int) -> bool:
     """Finite and >= 0 (-0.0 passes: it is a zero); 4-bit: and none in (0, Q4_MIN_SCALE)."""
     ok = np.isfinite(scale).all() and (scale >= 0).all()
-    return bool(ok and (bits == 8 or ((scale == 0) | (scale >= Q4_MIN_SCALE)).all()))
+    return bool(ok and (bits != 4 or ((scale == 0) | (scale >= Q4_MIN_SCALE)).all()))
 
 
 # -- the client's side -----------------------------------------------------------------------------
@@ -179,9 +212,14 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
     clip(rint(fl32(x / s)), -127, 127) (round half to even); s == 0 (an all-zero block, or amax / 127
     underflowing) gives codes 0 and scale 0.  stochastic: x / s is rounded up with probability equal
     to its fractional part (unbiased), with `rng` (a numpy.random.Generator).  center: x - center is
-    quantized, in fp32, and the entry is marked delta.  Non-finite input: ValueError."""
-    if bits not in _BLOCK_OF:
-        raise ValueError(f"bits must be 8 or 4, got {bits!r}")
+    quantized, in fp32, and the entry is marked delta.  Non-finite input: ValueError.  bits=1: blocks of
+    128, the code is x < 0 and s = fl32(the float64 mean of |x| over the block's real elements), the
+    minimiser of the block's squared error for sign codes; stochastic=True is refused (the unbiased 1-bit
+    rule needs s = max|x|: another scale)."""
+    if isinstance(bits, bool) or bits not in _BLOCK_OF:
+        raise ValueError(f"{_BITS_MSG}, got {bits!r}")
+    if bits == 1 and stochastic:
+        raise ValueError("stochastic rounding is not defined for bits=1 (the scale is the mean magnitude)")
     block, top = _BLOCK_OF[bits], _LEVELS[bits]
     x = np.asarray(x)
     if x.dtype != _F32:
@@ -196,6 +234,12 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
             flat = flat - np.ascontiguousarray(c, dtype=np.float32).reshape(-1)
     if not np.isfinite(flat).all():
         raise ValueError("non-finite values cannot be quantized")
+    if bits == 1:
+        b = _blocks(np.abs(flat).astype(np.float64), block)
+        real = np.minimum(block, flat.size - block * np.arange(b.shape[0]))  # the last block's real elements
+        scale = (b.sum(axis=1) / real).astype(np.float32)
+        return {"q1": pack_signs(flat < 0), "shape": tuple(shape), "scale": scale, "block": block,
+                "delta": center is not None}
     b = _blocks(flat, block)
     s = (np.abs(b).max(axis=1, initial=np.float32(0)) / np.float32(top)).astype(np.float32)
     live = s > 0 if bits == 8 else s >= Q4_MIN_SCALE
@@ -217,14 +261,19 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
 
 
 def dequantize_entry(e, center=None, key=None) -> np.ndarray:
-    """fl32(scale[b] * float(q)), and fl32(center + that) for a delta entry: the client's values."""
+    """fl32(scale[b] * float(q)) — 1-bit: scale[b] with the code's sign — and fl32(center + that) for a
+    delta entry: the client's values."""
     codes, scale, delta = check_entry(key, e)
     shape = entry_shape(e)
+    numel = int(np.prod(shape, dtype=np.int64))
     if "q4" in e:
-        codes = unpack_nibbles(codes, int(np.prod(shape, dtype=np.int64)))
+        codes = unpack_nibbles(codes, numel)
     block = _BLOCK_OF[bits_of(e)]
-    with np.errstate(over="ignore"):  # a scale near the top of the range: the product is +-inf, as on the device
-        x = (_blocks(codes.reshape(-1).astype(np.float32), block) * scale[:, None]).astype(np.float32).reshape(-1)[: codes.size]
+    if "q1" in e:
+        x = np.copysign(np.repeat(scale, block)[:numel], np.where(unpack_signs(codes, numel), np.float32(-1), np.float32(1)))
+    else:
+        with np.errstate(over="ignore"):  # a scale near the top of the range: the product is +-inf, as on the device
+            x = (_blocks(codes.reshape(-1).astype(np.float32), block) * scale[:, None]).astype(np.float32).reshape(-1)[: codes.size]
     if delta:
         if center is None:
             raise ValueError(f"key {key!r}: a delta entry needs the centre it was taken against")
@@ -239,9 +288,12 @@ def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None, bit
     """A state dict (numpy arrays or host torch tensors) as a quantized upload's params: every fp32
     tensor becomes a quantized entry (quantize_array), tensors of other dtypes are passed on as numpy
     arrays, float16 raises TypeError.  center: a w_glob-like dict; its values, cast to fp32, are
-    subtracted before quantizing and the entries are marked delta=True.  bits: 8 or 4."""
-    if bits not in _BLOCK_OF:
-        raise ValueError(f"bits must be 8 or 4, got {bits!r}")
+    subtracted before quantizing and the entries are marked delta=True.  bits: 8, 4 or 1 (1: no
+    stochastic rounding)."""
+    if isinstance(bits, bool) or bits not in _BLOCK_OF:
+        raise ValueError(f"{_BITS_MSG}, got {bits!r}")
+    if bits == 1 and stochastic:
+        raise ValueError("stochastic rounding is not defined for bits=1 (the scale is the mean magnitude)")
     if stochastic and rng is None:
         raise ValueError("stochastic rounding needs rng (a numpy.random.Generator)")
     out = {}
@@ -287,8 +339,8 @@ def check_round(w_local_lst, keys):
     """(qkeys, delta, entries, scales, bits) of a round of quantized uploads over the selected `keys`,
     or client-data errors.  qkeys: the selected keys that are quantized, in order; delta: the round's
     flag; entries[i][key] = (codes, scale) as checked host arrays (q8: int8 of the tensor's shape, q4:
-    the packed uint8 bytes); scales[i]: client i's scales of all qkeys in order, one array; bits: the
-    round's code width, 8 or 4.  ValueError: q4 and q8 entries in one round (across clients or keys),
+    and q1: the packed uint8 bytes); scales[i]: client i's scales of all qkeys in order, one array; bits:
+    the round's code width, 8, 4 or 1.  ValueError: entries of two widths in one round (across clients or keys),
     a key quantized by some clients and plain in others, a
     plain fp32 tensor, mixed delta flags, codes of different shapes, and check_entry's; TypeError:
     float16 tensors, and check_entry's.  A well-formed numpy entry costs a few attribute reads; a
@@ -315,12 +367,15 @@ def check_round(w_local_lst, keys):
                 bits = bits_of(v)
             elif bits_of(v) != bits:
                 raise ValueError(f"client {i} key {k!r}: {bits_of(v)}-bit codes in a round of {bits}-bit uploads "
-                                 "(a round's uploads are all q8 or all q4)")
-            if bits == 4:
-                q8, sc, d, shape = v.get("q4"), v.get("scale"), v.get("delta"), v.get("shape")
+                                 + ("(a round's uploads are all q8 or all q4)" if {bits, bits_of(v)} == {8, 4} else
+                                    "(a round's uploads are all of one width: q8, q4 or q1)"))
+            if bits in _PACKED:
+                tag, per = _PACKED[bits]
+                q8, sc, d, shape = v.get(tag), v.get("scale"), v.get("delta"), v.get("shape")
                 if not (type(q8) is np.ndarray and type(sc) is np.ndarray and q8.dtype == np.uint8 and sc.dtype == _F32
-                        and type(shape) is tuple and all(type(n) is int and n >= 0 for n in shape) and "q8" not in v
-                        and q8.ndim == 1 and q8.shape[0] == (math.prod(shape) + 1) // 2 and sc.ndim == 1
+                        and type(shape) is tuple and all(type(n) is int and n >= 0 for n in shape)
+                        and sum(t in v for t in ("q8", "q4", "q1")) == 1
+                        and q8.ndim == 1 and q8.shape[0] == (math.prod(shape) + per - 1) // per and sc.ndim == 1
                         and sc.shape[0] == n_blocks(math.prod(shape), Q4_BLOCK) and type(v.get("block")) is int
                         and v["block"] == Q4_BLOCK and type(d) is bool and q8.flags.c_contiguous and sc.flags.c_contiguous):
                     q8, sc, d = check_entry(k, v, i)  # raises what is wrong, or hands back the packed bytes as host arrays

@@ -1,9 +1,17 @@
 """The quantized round of the engine, bound on Aggregator as `ensemble_quantized` (DESIGN.md
-sections 17 and 18): uploads whose fp32 tensors are int8 or int4 block-quantized entries (quant.py)
-are summed by ops.deq_fold_stack / ops.deq_fold_q4_stack from a device stack of one byte, or half a
-byte, per parameter — the codes are never expanded to fp32 in memory — and the round ends in the
-server step every round ends in (Aggregator._server_step).  The two widths differ in their layout
-constants (_LAYOUT) and in how a key's codes are indexed; the round is one.
+sections 17, 18 and 21): uploads whose fp32 tensors are int8, int4 or 1-bit sign block-quantized
+entries (quant.py) are summed by ops.deq_fold_stack / ops.deq_fold_q4_stack / ops.deq_fold_q1_stack
+from a device stack of one byte, half a byte, or one bit per parameter — the codes are never expanded
+to fp32 in memory — and the round ends in the server step every round ends in
+(Aggregator._server_step).  The widths differ in their layout constants (_LAYOUT) and in how a key's
+codes are indexed; the round is one.
+
+Padding.  A key ends on a scale block's boundary and the row on a chunk's.  Padding columns hold code 0,
+and whole padding blocks scale 0.  For 8 and 4 bits code 0 is the value 0; a sign code has no zero, so
+the padding columns inside a 1-bit key's last block hold +scale and their sums are not 0.  Nothing
+reads them: the server step's results and the server optimiser's state are copied out per segment
+(offset, numel), a fused update works column by column, and no launch of this round reduces across
+columns.
 """
 from __future__ import annotations
 
@@ -35,7 +43,8 @@ def _refuse(agg, server_opt) -> None:
 # per code width: (columns per scale, columns the row stride is a multiple of, columns per byte, the
 # stack's dtype, the staging buffers' tag, the device entry)
 _LAYOUT = {8: (quant.BLOCK, quant.BLOCK, 1, torch.int8, "q8", ops.deq_fold_stack),
-           4: (quant.Q4_BLOCK, na.Q4_CHUNK, 2, torch.uint8, "q4", ops.deq_fold_q4_stack)}
+           4: (quant.Q4_BLOCK, na.Q4_CHUNK, 2, torch.uint8, "q4", ops.deq_fold_q4_stack),
+           1: (quant.Q1_BLOCK, na.Q1_CHUNK, 8, torch.uint8, "q1", ops.deq_fold_q1_stack)}
 
 
 def _stand_ins(w_local_lst, keys, qkeys, entries):
@@ -52,7 +61,7 @@ def _stand_ins(w_local_lst, keys, qkeys, entries):
 
 
 def _q_plan(plan: BucketPlan, bits: int) -> BucketPlan:
-    """`plan` with its fp32 group laid out for fa_deq_fold_q8 / _q4: every segment starts on a scale
+    """`plan` with its fp32 group laid out for fa_deq_fold_q8 / _q4 / _q1: every segment starts on a scale
     block's boundary (1024 / 128 columns: one scale block never spans two keys) and the stride is a
     multiple of 1024 / 2048 columns.  Kept in the base plan's memo: make_plan reuses plans across rounds."""
     block, chunk, _, _, tag, _ = _LAYOUT[bits]
@@ -76,7 +85,8 @@ def _q_plan(plan: BucketPlan, bits: int) -> BucketPlan:
 def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, device, bits: int = 8):
     """Clients [lo, hi) as one pinned int8 [K, stride] code stack and one fp32 [K, stride / 1024] scale
     stack on the device — for 4-bit codes uint8 [K, stride / 2], a key's packed bytes copied as they
-    are to byte offset / 2, and scales [K, stride / 128]; padding is code 0 with scale 0.  Rows are
+    are to byte offset / 2, and scales [K, stride / 128]; 1-bit codes the same with eight columns per
+    byte (a key starts on a multiple of 128 columns: a whole byte); padding is code 0 with scale 0.  Rows are
     packed in groups (the packer's threads, one row range each) and every group's H2D is queued while
     the next is packed.  Returns the two device tensors."""
     block, _, per_byte, dtype, tag, _ = _LAYOUT[bits]
@@ -129,12 +139,14 @@ def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, d
 
 def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_opt: ServerOptimizer | None = None,
                        center=None):
-    """The weighted mean of int8 or int4 block-quantized uploads (quant.py's formats; FedPAQ,
+    """The weighted mean of int8, int4 or 1-bit block-quantized uploads (quant.py's formats; FedPAQ,
     Reisizadeh et al. 2020), bit-identical to ensemble(agg_weight_lst, the dequantized uploads, key_lst,
     server_opt).  What follows describes the int8 round; a round of 4-bit uploads (routed on what the
     uploads hold) is the same with segments on 128-column boundaries, a stride that is a multiple of
     2048 columns, a uint8 [N, stride / 2] stack, scales [N, stride / 128] and ops.deq_fold_q4_stack,
-    and its audit carries "bits": 4 (an int8 round's audit is as it was: last_quant.get("bits", 8)).
+    and its audit carries "bits": 4 (an int8 round's audit is as it was: last_quant.get("bits", 8)); a
+    round of 1-bit uploads has the same segments and stride, a uint8 [N, stride / 8] stack,
+    ops.deq_fold_q1_stack and "bits": 1.
 
     The round is planned with the plan's own numerics (make_plan over zero-strided fp32 stand-ins of
     the quantized keys), its fp32 group re-laid with segments on 1024-column boundaries; the codes are
@@ -196,7 +208,7 @@ def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_op
             deq_fold(dq, ds, weights[lo:hi], acc if lo else None, acc, center=row, n_clients=hi - lo)
     nb = g32.stride // block
     agg.last_quant = {"bytes_in": n * g32.stride // per_byte + 4 * n * nb, "bytes_fp32": 4 * n * base.groups[KIND_F32].stride,
-                      "delta": delta, "blocks": n * nb, **({"bits": 4} if bits == 4 else {})}
+                      "delta": delta, "blocks": n * nb, **({"bits": bits} if bits != 8 else {})}
     sums = {KIND_F32: [(packer.shards(plan, KIND_F32)[0], ops.FoldedSum(acc, na.ACC_F32, n, g32.stride))]}
     for kind, parts in stacks8.items():
         sums[kind] = parts

@@ -1,4 +1,4 @@
-"""FedAVG over int8 or int4 block-quantized uploads (quant.py, quantround.py; DESIGN.md sections 17, 18)."""
+"""FedAVG over int8, int4 or 1-bit block-quantized uploads (quant.py, quantround.py; DESIGN.md sections 17, 18, 21)."""
 from __future__ import annotations
 
 import numpy as np
@@ -38,14 +38,25 @@ class QuantizedAVG(AVG):
     mixing the two is refused.  One device; chunk_clients=K folds a quantized round in chunks of K
     clients.  Client-data errors take server_exception's route.  bits=4 (`setup_strategy("avg_q4")`):
     clients upload 4-bit codes, two per byte, with one scale per 128 (an eighth of the fp32 bytes); the
-    server routes on what the uploads hold."""
+    server routes on what the uploads hold.  bits=1 (`setup_strategy("avg_q1")`): a sign per parameter and
+    a magnitude per 128, 1.25 bits per parameter (scaled signSGD); stochastic=True is refused.  Sign
+    compression is biased and does not converge alone, so error_feedback (EF-signSGD, Karimireddy et al.
+    2019; the default for bits=1 and refused for the other widths) has the client instance keep the fp32
+    residual e of its last upload: it quantizes x + e (the update x + e - g when delta is on) and sets e
+    to what it quantized minus what the server will read.  The server's work is the same."""
 
     def __init__(self, server_opt=None, delta=True, stochastic=False, seed=None, encrypt=None, output="reference",
-                 device=None, chunk_clients=None, bits=8):
-        if isinstance(bits, bool) or bits not in (8, 4):
-            raise ValueError(f"bits must be 8 or 4, got {bits!r}")
+                 device=None, chunk_clients=None, bits=8, error_feedback=None):
+        if isinstance(bits, bool) or bits not in (8, 4, 1):
+            raise ValueError(f"bits must be 8, 4 or 1, got {bits!r}")
+        if error_feedback not in (None, False, True) or (error_feedback and bits != 1):
+            raise ValueError(f"error_feedback is bits=1's (True, False or None), got {error_feedback!r} with bits={bits!r}")
+        if bits == 1 and stochastic:
+            raise ValueError("stochastic rounding is not defined for bits=1")
         super().__init__(encrypt, output, device, None, None, chunk_clients)
         self.bits = int(bits)
+        self.error_feedback = bits == 1 and error_feedback is not False
+        self._residual = {}  # the client's: key -> what its last upload quantized minus its dequantized value
         self.server_opt = server_opt
         self.delta = bool(delta)
         self.stochastic = bool(stochastic)
@@ -64,8 +75,27 @@ class QuantizedAVG(AVG):
         """Upload the state_dict quantized: against the last received w_glob when delta is on and
         there is one, else as it is."""
         center = self._received if self.delta else None
-        params = quant.quantize_state_dict(convert_to_np(trainer.weight), center, self.stochastic, self._rng, self.bits)
+        sd = convert_to_np(trainer.weight)
+        if self.error_feedback:
+            return {"agg_weight": agg_weight, "params": self._quantize_with_feedback(sd, center)}
+        params = quant.quantize_state_dict(sd, center, self.stochastic, self._rng, self.bits)
         return {"agg_weight": agg_weight, "params": params}
+
+    def _quantize_with_feedback(self, sd, center):
+        """quantize_state_dict of x + e, e the residual kept from the last upload (zero at first, and for
+        a tensor whose shape changed); then e = u - the entry's dequantized value, u being what was
+        quantized: fl32(x + e), less the centre for a delta upload.  All in fp32."""
+        fed = {}
+        for k, v in sd.items():
+            a = np.asarray(v)
+            e = self._residual.get(k)
+            fed[k] = a + e if a.dtype == np.float32 and e is not None and e.shape == a.shape else v
+        params = quant.quantize_state_dict(fed, center, False, None, self.bits)
+        for k, entry in params.items():
+            if quant.is_entry(entry):
+                u = fed[k] - np.asarray(center[k], dtype=np.float32) if center is not None else fed[k]
+                self._residual[k] = u - quant.dequantize_entry(dict(entry, delta=False), None, k)
+        return params
 
     def client_receive(self, trainer, server_p_bytes):
         """AVG's, and an fp32 copy of the received w_glob is kept as the next upload's centre."""

@@ -24,7 +24,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     (engine), server_side (AVGM / OPT), trim, server_opt and wide (TrimmedMean; Median: all but trim),
     f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
     server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
-    server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes),
+    server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes; "avg_q1": 1-bit sign codes,
+    stochastic refused, and error_feedback),
     server_opt, stochastic and seed (BF16AVG, "avg_bf16")."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
@@ -63,6 +64,10 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "avg_q4": lambda: QuantizedAVG(
             strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False),
             strategy_p.get("seed"), **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}, bits=4),
+        "avg_q1": lambda: QuantizedAVG(
+            strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False), strategy_p.get("seed"),
+            **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}, bits=1,
+            error_feedback=strategy_p.get("error_feedback")),
         "avg_bf16": lambda: BF16AVG(
             strategy_p.get("server_opt"), strategy_p.get("stochastic", False), strategy_p.get("seed"),
             **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}),

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 26
+#define FA_ABI_VERSION 27
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 / fa_deq_fold_q1 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -575,6 +575,37 @@ int fa_deq_fold_q4(const uint8_t* stack, int64_t row_stride, int32_t n_clients, 
  * instantiation, e.g. "widen_fold_kernel<4,4,4,true>", launches = 1.                              */
 int fa_fold_bf16(const uint16_t* stack, int64_t row_stride, int32_t n_clients, const float* weights,
                  const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols, void* stream);
+
+/* ---- 1-bit sign uploads (ABI 27) -------------------------------------------
+ * A sign-quantized client row is one bit per column, eight per byte — column c is bit c % 8 of byte
+ * c / 8, 1 = negative — and one fp32 scale (a magnitude: finite and >= 0) per FA_Q1_BLOCK columns of
+ * the row (block b covers columns [128 b, 128 b + 128)): scaled signSGD's format, 1.25 bits per
+ * column.  There is no reference counterpart.  fa_deq_fold_q1 is fa_deq_fold_q4 for such rows.  Per
+ * column c of the window and row i, every operation rounded to fp32 and none contracted:
+ *   x   = copysign(scales[i * scale_stride + (col_begin + c) / 128], bit ? -1 : +1)   (a bit pattern)
+ *   x   = fl32(center[col_begin + c] + x)                      when center != NULL (delta uploads)
+ *   acc = fl32(acc + fl32(weights[i] * x))                     in list order
+ * acc starts from acc_in[c]; acc_in == NULL opens the round: acc = fl32(weights[0] * x_0), the other
+ * rows added — fa_fold's (FA_ACC_F32) bits on the dequantized rows, -0.0 and overflow to inf
+ * included; only a NaN's bits are free.  Columns are elements: row_stride is in BYTES, so a row holds
+ * 8 * row_stride columns; scale_stride is in floats per client row; center is indexed by absolute
+ * column, acc_in / acc_out from 0 at col_begin.  acc_out may be acc_in.  Weights and scales are read
+ * from device memory per row: no client cap.
+ * FA_ERR_ARG: a NULL stack / scales / weights / acc_out, n_clients < 1, n_cols < 0, a window
+ * outside the row or whose last block is past scale_stride, or acc_in overlapping acc_out within
+ * n_cols elements without equalling it.  FA_ERR_ALIGN: stack / center / acc_in / acc_out not
+ * 16-byte aligned, row_stride no multiple of 16, col_begin no multiple of FA_Q1_CHUNK (one wave's
+ * 4-byte loads: 2048 columns), scales / weights not 4-byte aligned.  Every error is decided before
+ * any HIP call.  n_cols == 0 is a no-op that launches nothing.  Code rows are read through a range
+ * rounded up to 4 bytes (inside the row); nothing outside acc_out[0, n_cols) is written.
+ * fa_set_reduce_grid applies; fa_last_launch names the instantiation,
+ * "sign_fold_kernel<1,8,4,true>", launches = 1.                                                  */
+#define FA_Q1_BLOCK 128
+#define FA_Q1_CHUNK 2048
+int fa_deq_fold_q1(const uint8_t* stack, int64_t row_stride, int32_t n_clients, const float* scales,
+                   int64_t scale_stride, const float* weights, const float* center,
+                   const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
+                   void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

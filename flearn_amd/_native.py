@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 27
+ABI_VERSION = 28
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -36,6 +36,9 @@ GRAM_MAX_CLIENTS = 128  # fa_gram_f32's (FA_GRAM_MAX_CLIENTS)
 Q8_BLOCK = 1024  # columns per scale of a quantized row (FA_Q8_BLOCK)
 Q4_BLOCK, Q4_CHUNK = 128, 2048  # of a 4-bit quantized row, and fa_deq_fold_q4's col_begin unit (FA_Q4_BLOCK, FA_Q4_CHUNK)
 Q1_BLOCK, Q1_CHUNK = 128, 2048  # of a 1-bit sign row, and fa_deq_fold_q1's col_begin unit (FA_Q1_BLOCK, FA_Q1_CHUNK)
+MX_BLOCK, MX_CHUNK = 32, 2048  # of a Microscaling row, and fa_deq_fold_mx's col_begin unit (FA_MX_BLOCK, FA_MX_CHUNK)
+MX_FP4, MX_FP8 = 4, 8  # fa_deq_fold_mx's element types (FA_MX_FP4, FA_MX_FP8)
+MX_MIN_EXP, MX_MAX_EXP = 27, 227  # the legal E8M0 scale bytes (FA_MX_MIN_EXP, FA_MX_MAX_EXP)
 CLIP_MAX_CLIENTS = 128  # fa_rownorm2_f32's and fa_clip_sum_f32's (FA_CLIP_MAX_CLIENTS)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
@@ -85,6 +88,7 @@ EXPORTS = (
     "fa_deq_fold_q4",
     "fa_fold_bf16",
     "fa_deq_fold_q1",
+    "fa_deq_fold_mx",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -269,6 +273,7 @@ def load(require_gpu: bool = False):
                 "fa_deq_fold_q4": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_fold_bf16": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_deq_fold_q1": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
+                "fa_deq_fold_mx": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, I32, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

@@ -7,7 +7,7 @@ makes the accumulator of a robust round (per column, the sorted clients' middle 
 the clients' Gram matrix, `rownorm2_stack` their squared update norms and `clip_sum_stack` the
 accumulator of a norm-clipped round, to which `gauss_add` adds a DP-FedAvg round's noise;
 `deq_fold_stack` adds a chunk of int8 block-quantized client rows to an fp32 accumulator and
-`deq_fold_q4_stack` one of int4 rows, two codes per byte, `deq_fold_q1_stack` one of sign rows, eight
+`deq_fold_q4_stack` one of int4 rows, two codes per byte, `deq_fold_mx_stack` one of MXFP4 / MXFP8 rows, `deq_fold_q1_stack` one of sign rows, eight
 bits per byte with a magnitude per 128; `fold_bf16_stack` adds a chunk of
 bfloat16 client rows, widened in registers.  `StackSum`
 and `FoldedSum` carry what differs between those two ways to a round's weighted sum behind one
@@ -500,9 +500,27 @@ def deq_fold_q1_stack(stack_u8: torch.Tensor, scales: torch.Tensor, weights: tor
               col_begin, n_cols, n_clients)
 
 
-def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_in, acc_out, center, col_begin, n_cols, n_clients):
-    """The checks and the call deq_fold_stack, deq_fold_q4_stack and deq_fold_q1_stack share: `stack` holds `per_byte`
-    columns per byte and one scale per `block` columns."""
+def deq_fold_mx_stack(codes: torch.Tensor, scales: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+                      center: torch.Tensor | None = None, n_clients: int | None = None, elem: int, col_begin: int = 0,
+                      n_cols: int | None = None) -> None:
+    """deq_fold_stack for OCP Microscaling rows (fa_deq_fold_mx; DESIGN.md section 22, restated by
+    tests/mx_ref.py).  elem = na.MX_FP4: codes is uint8 [N, stride bytes] holding 2 * stride E2M1 columns
+    per row, column c a nibble of byte c // 2, the low one for even c; elem = na.MX_FP8: one E4M3 code
+    per byte.  stride a multiple of 16.  scales: uint8 [N, >= ceil((col_begin + n_cols) / 32)] E8M0
+    bytes in na.MX_MIN_EXP ... na.MX_MAX_EXP, a row stride that is a multiple of 4.
+    x = decode(code) * 2^(scales[i, (col_begin + c) // 32] - 127), exact; the rest as deq_fold_stack;
+    col_begin a multiple of 2048.  The bits are fold_stack's (na.ACC_F32) on the dequantized rows."""
+    if elem not in (na.MX_FP4, na.MX_FP8):
+        raise ValueError(f"elem must be na.MX_FP4 or na.MX_FP8, got {elem!r}")
+    _deq_fold("fa_deq_fold_mx", "codes", torch.uint8, 8 // elem, na.MX_BLOCK, codes, scales, weights, acc_in, acc_out, center,
+              col_begin, n_cols, n_clients, torch.uint8, (elem,))
+
+
+def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_in, acc_out, center, col_begin, n_cols, n_clients,
+              scale_dtype=torch.float32, extra=()):
+    """The checks and the call deq_fold_stack, deq_fold_q4_stack, deq_fold_q1_stack and deq_fold_mx_stack share:
+    `stack` holds `per_byte` columns per byte and one scale of `scale_dtype` per `block` columns; `extra` goes
+    between n_cols and the stream."""
     if (not isinstance(stack, torch.Tensor) or stack.dim() != 2 or stack.stride(1) != 1
             or not stack.is_cuda):
         raise ValueError(f"{what} must be a 2-D device tensor with contiguous rows")
@@ -511,9 +529,9 @@ def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_i
     n, ncols = _check_window((stack.shape[0], stack.shape[1] * per_byte), col_begin, n_cols, n_clients)
     dev = stack.device
     blocks = -(-(col_begin + ncols) // block)
-    if (not isinstance(scales, torch.Tensor) or scales.dtype != torch.float32 or scales.device != dev
+    if (not isinstance(scales, torch.Tensor) or scales.dtype != scale_dtype or scales.device != dev
             or scales.dim() != 2 or scales.stride(1) != 1 or scales.shape[0] < n or scales.shape[1] < blocks):
-        raise ValueError(f"scales must be a torch.float32 [>= {n}, >= {blocks}] tensor with contiguous rows on the "
+        raise ValueError(f"scales must be a {scale_dtype} [>= {n}, >= {blocks}] tensor with contiguous rows on the "
                          "stack's device")
     if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != dev
             or not weights.is_contiguous() or weights.numel() < n):
@@ -529,7 +547,7 @@ def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_i
                              "stack's device")
     rc = getattr(na.lib(), entry)(stack.data_ptr(), stack.stride(0), n, scales.data_ptr(), scales.stride(0),
                                   weights.data_ptr(), _ptr(center), _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols,
-                                  na.stream_handle(dev))
+                                  *extra, na.stream_handle(dev))
     na.check(rc, entry)
 
 

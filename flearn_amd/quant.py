@@ -1,4 +1,4 @@
-"""Int8, int4 and 1-bit sign block-quantized uploads (DESIGN.md sections 17, 18 and 21): the formats,
+"""Int8, int4, 1-bit sign and Microscaling block-quantized uploads (DESIGN.md sections 17, 18, 21 and 22): the formats,
 their checks, and the client's quantizer and dequantizer.  Host-side numpy only, no device code.
 
 A quantized entry of upload["params"] replaces an fp32 tensor of shape S by a plain dict
@@ -37,6 +37,20 @@ copysign(scale[b], -1 if bit else +1) — a bit pattern, not a product — plus 
 entry.  A sign code has no zero: the quantizer is biased, and a client keeps the residual
 (QuantizedAVG's error_feedback).  Spare bits are ignored on receipt, as q4's spare nibble is.
 
+The Microscaling entries (format="mx"; OCP Microscaling Formats v1.0) scale blocks of 32 by a power of two:
+
+    {"mx4": uint8 ndarray [ceil(numel / 2)], "shape": tuple S, "scale": uint8 ndarray [ceil(numel / 32)],
+     "block": 32, "delta": bool}            MXFP4: E2M1 codes, two per byte, the low nibble the even element
+    {"mx8": uint8 ndarray [numel], ...}     MXFP8: E4M3 "fn" codes, one per byte
+
+A scale byte e is E8M0 and stands for 2^(e - 127); legal bytes are MX_MIN_EXP = 27 ... MX_MAX_EXP = 227
+(2^-100 ... 2^100; 255, E8M0's NaN, is refused with the rest), where every decoded value of both element
+types is zero or an fp32 normal, and exact.  An E2M1 code is sign, two exponent bits and a mantissa bit:
++-0, 0.5, 1, 1.5, 2, 3, 4, 6, no inf, no NaN, -0 legal and -0.0.  An E4M3 code has bias 7, maximum 448,
+subnormals down to 2^-9, no inf; S.1111.111 is NaN: legal on receipt (the sums are NaN), never emitted.
+The value is decode(code) * 2^(e - 127), an exact fp32, plus the centre for a delta entry.  One round's
+uploads are all of one format and element type.
+
 Block-wise absmax scaling as in Dettmers et al. (ICLR 2022); quantized client updates as in FedPAQ
 (Reisizadeh et al., AISTATS 2020); the stochastic rounding is QSGD's (Alistarh et al., NeurIPS 2017).
 """
@@ -56,6 +70,43 @@ _BLOCK_OF = {8: BLOCK, 4: Q4_BLOCK, 1: Q1_BLOCK}
 _LEVELS = {8: 127, 4: 7, 1: 1}
 _PACKED = {4: ("q4", 2), 1: ("q1", 8)}  # the widths whose codes are packed bytes: (field, codes per byte)
 _BITS_MSG = "bits must be 8, 4 or 1"
+MX_BLOCK = 32  # FA_MX_BLOCK: one lane of fa_deq_fold_mx's wave-chunk
+MX_MIN_EXP, MX_MAX_EXP = 27, 227  # FA_MX_MIN_EXP, FA_MX_MAX_EXP: the legal E8M0 scale bytes
+_MX = {"mx4": 2, "mx8": 1}  # the Microscaling tags: codes per byte
+_MX_EMAX = {"mx4": 2, "mx8": 8}  # the exponent of the element format's largest binade (6 = 1.5 * 2^2, 448 = 1.75 * 2^8)
+_TAGS = ("q8", "q4", "q1", "mx4", "mx8")
+
+
+def _mx_table(tag: str) -> np.ndarray:
+    """decode(code) for every code of an element type, in float64 from the format's definition."""
+    ebits, mbits, bias = (2, 1, 1) if tag == "mx4" else (4, 3, 7)
+    c = np.arange(1 << (1 + ebits + mbits))
+    ex, man = (c >> mbits) & ((1 << ebits) - 1), c & ((1 << mbits) - 1)
+    mag = np.where(ex == 0, man * 2.0 ** (1 - bias - mbits), (1 + man * 2.0 ** -mbits) * 2.0 ** (ex - bias))
+    if tag == "mx8":
+        mag[(c & 0x7F) == 0x7F] = np.nan
+    return np.copysign(mag, np.where(c >> (ebits + mbits), -1.0, 1.0))
+
+
+MX_TABLE = {tag: _mx_table(tag) for tag in _MX}
+
+
+def _check_format(bits, format) -> str | None:
+    """The Microscaling tag of (bits, format), None for format="int"; ValueError for what is neither."""
+    if isinstance(bits, bool) or bits not in _BLOCK_OF:
+        raise ValueError(f"{_BITS_MSG}, got {bits!r}")
+    if format == "int":
+        return None
+    if format != "mx":
+        raise ValueError(f'format must be "int" or "mx", got {format!r}')
+    if bits == 1:
+        raise ValueError('format="mx" has 4-bit (MXFP4) and 8-bit (MXFP8) elements: bits=1 is not a Microscaling format')
+    return f"mx{bits}"
+
+
+def width_of(e):
+    """What a round's entries must agree on: 8, 4 or 1 for the integer codes, "mx4" / "mx8"."""
+    return "mx4" if "mx4" in e else "mx8" if "mx8" in e else bits_of(e)
 
 
 def n_blocks(numel: int, block: int = BLOCK) -> int:
@@ -63,18 +114,18 @@ def n_blocks(numel: int, block: int = BLOCK) -> int:
 
 
 def is_entry(v) -> bool:
-    """v is (shaped like) a quantized entry: a dict with a "q8", a "q4" or a "q1"."""
-    return isinstance(v, dict) and ("q8" in v or "q4" in v or "q1" in v)
+    """v is (shaped like) a quantized entry: a dict with a "q8", a "q4", a "q1", an "mx4" or an "mx8"."""
+    return isinstance(v, dict) and ("q8" in v or "q4" in v or "q1" in v or "mx4" in v or "mx8" in v)
 
 
 def bits_of(e) -> int:
     """The code width of a quantized entry."""
-    return 4 if "q4" in e else 1 if "q1" in e else 8
+    return 4 if "q4" in e or "mx4" in e else 1 if "q1" in e else 8
 
 
 def entry_shape(e) -> tuple:
     """The shape of the tensor an entry stands for."""
-    return tuple(e["shape"]) if "q4" in e or "q1" in e else tuple(e["q8"].shape)
+    return tuple(e["q8"].shape) if "q8" in e and "shape" not in e else tuple(e["shape"])
 
 
 def pack_nibbles(codes: np.ndarray) -> np.ndarray:
@@ -126,6 +177,8 @@ def check_entry(key, e, client=None):
     NaN or inf, and a missing field; TypeError for a q8 that is no int8 array (a device-resident one
     included) and a scale that is no float32 array."""
     where = f"key {key!r}" if client is None else f"client {client} key {key!r}"
+    if "mx4" in e or "mx8" in e:
+        return _check_entry_mx(where, e)
     if "q4" in e:
         return _check_entry4(where, e)
     if "q1" in e:
@@ -188,8 +241,48 @@ def _check_entry4(where: str, e, bits: int = 4):
     return np.ascontiguousarray(q4), np.ascontiguousarray(scale), bool(e["delta"])
 
 
-def _scales_ok(scale: np.ndarray, bits: int) -> bool:
-    """Finite and >= 0 (-0.0 passes: it is a zero); 4-bit: and none in (0, Q4_MIN_SCALE)."""
+def _check_entry_mx(where: str, e):
+    """check_entry for a Microscaling entry: (the code bytes as a C-contiguous uint8 array, the scale bytes,
+    delta).  ValueError: a missing field, codes of two kinds, a block other than 32, a malformed shape, a
+    code or scale count that does not fit it, a scale byte outside MX_MIN_EXP ... MX_MAX_EXP; TypeError:
+    codes or scales that are no uint8 array (device-resident ones included).  Every code is legal, E4M3's
+    NaNs too; an odd MXFP4 tensor's spare nibble is not looked at."""
+    tag = "mx4" if "mx4" in e else "mx8"
+    per = _MX[tag]
+    for f in (tag, "shape", "scale", "block", "delta"):
+        if f not in e:
+            raise ValueError(f"{where}: quantized entry lacks {f!r}")
+    if sum(t in e for t in _TAGS) > 1:
+        raise ValueError(f"{where}: an entry carries codes of one format, not {tag} and another")
+    if isinstance(e["block"], bool) or not isinstance(e["block"], (int, np.integer)) or int(e["block"]) != MX_BLOCK:
+        raise ValueError(f"{where}: block must be {MX_BLOCK} for Microscaling codes, got {e['block']!r}")
+    if not isinstance(e["delta"], (bool, np.bool_)):
+        raise ValueError(f"{where}: delta must be a bool, got {e['delta']!r}")
+    shape = e["shape"]
+    if not isinstance(shape, (tuple, list)) or not all(
+            isinstance(d, (int, np.integer)) and not isinstance(d, bool) and d >= 0 for d in shape):
+        raise ValueError(f"{where}: shape must be a tuple of non-negative ints, got {shape!r}")
+    numel = int(np.prod(shape, dtype=np.int64))
+    codes = _host_array(e[tag], f"{where} {tag}")
+    if codes.dtype != np.uint8:
+        raise TypeError(f"{where}: {tag} must be uint8, got {codes.dtype}")
+    if codes.ndim != 1 or codes.shape[0] != (numel + per - 1) // per:
+        raise ValueError(f"{where}: {numel} elements need {(numel + per - 1) // per} code bytes, got shape {tuple(codes.shape)}")
+    scale = _host_array(e["scale"], f"{where} scale")
+    if scale.dtype != np.uint8:
+        raise TypeError(f"{where}: Microscaling scales must be uint8 (E8M0), got {scale.dtype}")
+    if scale.ndim != 1 or scale.shape[0] != n_blocks(numel, MX_BLOCK):
+        raise ValueError(f"{where}: {numel} elements need {n_blocks(numel, MX_BLOCK)} scales, got shape {tuple(scale.shape)}")
+    if not _scales_ok(scale, tag):
+        raise ValueError(f"{where}: Microscaling scale bytes must be {MX_MIN_EXP} ... {MX_MAX_EXP} (2^-100 ... 2^100)")
+    return np.ascontiguousarray(codes), np.ascontiguousarray(scale), bool(e["delta"])
+
+
+def _scales_ok(scale: np.ndarray, bits) -> bool:
+    """Finite and >= 0 (-0.0 passes: it is a zero); 4-bit: and none in (0, Q4_MIN_SCALE); Microscaling
+    ("mx4" / "mx8"): bytes in MX_MIN_EXP ... MX_MAX_EXP."""
+    if bits in _MX:
+        return bool(((scale >= MX_MIN_EXP) & (scale <= MX_MAX_EXP)).all())
     ok = np.isfinite(scale).all() and (scale >= 0).all()
     return bool(ok and (bits != 4 or ((scale == 0) | (scale >= Q4_MIN_SCALE)).all()))
 
@@ -205,7 +298,38 @@ def _blocks(flat: np.ndarray, block: int = BLOCK) -> np.ndarray:
     return out.reshape(nb, block)
 
 
-def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=None, bits: int = 8) -> dict:
+def _floor_log2(a: np.ndarray) -> np.ndarray:
+    """floor(log2(a)) of positive floats, exactly (frexp: a = m * 2^e with 0.5 <= m < 1)."""
+    return np.frexp(a)[1].astype(np.int64) - 1
+
+
+def _quantize_mx(flat: np.ndarray, shape, tag: str, delta: bool) -> dict:
+    """quantize_array's Microscaling rule on the flat fp32 values (centre already subtracted, finite): per
+    block of 32, e = floor(log2(absmax)) - emax + 127 clamped into MX_MIN_EXP ... MX_MAX_EXP (an all-zero
+    block: MX_MIN_EXP); a code is x / 2^(e - 127) — exact in float64 — rounded to nearest even in the
+    element format and saturated at the format's maximum, found in the table of magnitudes."""
+    b = _blocks(flat.astype(np.float64), MX_BLOCK)
+    amax = np.abs(b).max(axis=1, initial=0.0)
+    e = np.full(amax.shape, MX_MIN_EXP, dtype=np.int64)
+    live = amax > 0
+    e[live] = np.clip(_floor_log2(amax[live]) - _MX_EMAX[tag] + 127, MX_MIN_EXP, MX_MAX_EXP)
+    r = np.ldexp(b, (127 - e)[:, None])
+    mbits, emin = (1, 0) if tag == "mx4" else (3, -6)  # mantissa bits, the smallest normal binade
+    mags = np.abs(MX_TABLE[tag][: 8 if tag == "mx4" else 127])  # the non-negative codes' values, ascending
+    a = np.abs(r)
+    ex = np.maximum(_floor_log2(np.where(a > 0, a, 1.0)), emin)
+    quantum = np.ldexp(1.0, ex - mbits)
+    q = np.minimum(np.rint(a / quantum) * quantum, mags[-1])  # rint: ties to the even mantissa
+    codes = np.searchsorted(mags, q).astype(np.uint8) | (np.signbit(r).astype(np.uint8) << (3 if tag == "mx4" else 7))
+    codes = codes.reshape(-1)[: flat.size]
+    if tag == "mx4":
+        if codes.size & 1:
+            codes = np.append(codes, np.uint8(0))
+        codes = codes[0::2] | (codes[1::2] << 4)
+    return {tag: codes, "shape": tuple(shape), "scale": e.astype(np.uint8), "block": MX_BLOCK, "delta": delta}
+
+
+def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=None, bits: int = 8, format: str = "int") -> dict:
     """One fp32 array as a quantized entry.  bits=4: blocks of 128, s = fl32(amax / 7), codes clipped
     to -7 ... 7 and packed two per byte, a block with s < 2^-100 gets scale 0 and codes 0, and
     |dequantized - x| <= s * (0.5 + 2^-20).  bits=8, per block: amax = max|x|, s = fl32(amax / 127), codes
@@ -215,9 +339,11 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
     quantized, in fp32, and the entry is marked delta.  Non-finite input: ValueError.  bits=1: blocks of
     128, the code is x < 0 and s = fl32(the float64 mean of |x| over the block's real elements), the
     minimiser of the block's squared error for sign codes; stochastic=True is refused (the unbiased 1-bit
-    rule needs s = max|x|: another scale)."""
-    if isinstance(bits, bool) or bits not in _BLOCK_OF:
-        raise ValueError(f"{_BITS_MSG}, got {bits!r}")
+    rule needs s = max|x|: another scale).  format="mx": bits=4 is MXFP4 and bits=8 MXFP8 (_quantize_mx has
+    the rule); stochastic=True is refused for it."""
+    tag = _check_format(bits, format)
+    if tag and stochastic:
+        raise ValueError('stochastic rounding is not implemented for format="mx"')
     if bits == 1 and stochastic:
         raise ValueError("stochastic rounding is not defined for bits=1 (the scale is the mean magnitude)")
     block, top = _BLOCK_OF[bits], _LEVELS[bits]
@@ -234,6 +360,8 @@ def quantize_array(x: np.ndarray, center=None, stochastic: bool = False, rng=Non
             flat = flat - np.ascontiguousarray(c, dtype=np.float32).reshape(-1)
     if not np.isfinite(flat).all():
         raise ValueError("non-finite values cannot be quantized")
+    if tag:
+        return _quantize_mx(flat, shape, tag, center is not None)
     if bits == 1:
         b = _blocks(np.abs(flat).astype(np.float64), block)
         real = np.minimum(block, flat.size - block * np.arange(b.shape[0]))  # the last block's real elements
@@ -268,8 +396,13 @@ def dequantize_entry(e, center=None, key=None) -> np.ndarray:
     numel = int(np.prod(shape, dtype=np.int64))
     if "q4" in e:
         codes = unpack_nibbles(codes, numel)
-    block = _BLOCK_OF[bits_of(e)]
-    if "q1" in e:
+    block = MX_BLOCK if width_of(e) in _MX else _BLOCK_OF[bits_of(e)]
+    if width_of(e) in _MX:
+        if "mx4" in e:
+            codes = np.stack([codes & 0xF, codes >> 4], axis=1).reshape(-1)
+        two = np.ldexp(1.0, scale.astype(np.int64) - 127)
+        x = (MX_TABLE[width_of(e)][codes[:numel]] * np.repeat(two, block)[:numel]).astype(np.float32)  # exact
+    elif "q1" in e:
         x = np.copysign(np.repeat(scale, block)[:numel], np.where(unpack_signs(codes, numel), np.float32(-1), np.float32(1)))
     else:
         with np.errstate(over="ignore"):  # a scale near the top of the range: the product is +-inf, as on the device
@@ -284,14 +417,14 @@ def dequantize_entry(e, center=None, key=None) -> np.ndarray:
     return x.reshape(shape)
 
 
-def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None, bits: int = 8) -> dict:
+def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None, bits: int = 8, format: str = "int") -> dict:
     """A state dict (numpy arrays or host torch tensors) as a quantized upload's params: every fp32
     tensor becomes a quantized entry (quantize_array), tensors of other dtypes are passed on as numpy
     arrays, float16 raises TypeError.  center: a w_glob-like dict; its values, cast to fp32, are
     subtracted before quantizing and the entries are marked delta=True.  bits: 8, 4 or 1 (1: no
-    stochastic rounding)."""
-    if isinstance(bits, bool) or bits not in _BLOCK_OF:
-        raise ValueError(f"{_BITS_MSG}, got {bits!r}")
+    stochastic rounding).  format: "int" or "mx" (Microscaling: bits 4 or 8, no stochastic rounding)."""
+    if _check_format(bits, format) and stochastic:
+        raise ValueError('stochastic rounding is not implemented for format="mx"')
     if bits == 1 and stochastic:
         raise ValueError("stochastic rounding is not defined for bits=1 (the scale is the mean magnitude)")
     if stochastic and rng is None:
@@ -309,7 +442,7 @@ def quantize_state_dict(sd, center=None, stochastic: bool = False, rng=None, bit
             if k not in center:
                 raise ValueError(f"center has no key {k!r}")
             c = np.asarray(_host_array(center[k], f"center[{k!r}]"), dtype=np.float32)
-        out[k] = quantize_array(a, c, stochastic, rng, bits)
+        out[k] = quantize_array(a, c, stochastic, rng, bits, format)
     return out
 
 
@@ -340,7 +473,7 @@ def check_round(w_local_lst, keys):
     or client-data errors.  qkeys: the selected keys that are quantized, in order; delta: the round's
     flag; entries[i][key] = (codes, scale) as checked host arrays (q8: int8 of the tensor's shape, q4:
     and q1: the packed uint8 bytes); scales[i]: client i's scales of all qkeys in order, one array; bits:
-    the round's code width, 8, 4 or 1.  ValueError: entries of two widths in one round (across clients or keys),
+    the round's code width, 8, 4 or 1, or its Microscaling tag, "mx4" / "mx8" (scales are then E8M0 bytes).  ValueError: entries of two widths in one round (across clients or keys),
     a key quantized by some clients and plain in others, a
     plain fp32 tensor, mixed delta flags, codes of different shapes, and check_entry's; TypeError:
     float16 tensors, and check_entry's.  A well-formed numpy entry costs a few attribute reads; a
@@ -364,20 +497,23 @@ def check_round(w_local_lst, keys):
                                      "(every fp32 tensor is quantized)")
                 continue
             if bits is None:
-                bits = bits_of(v)
-            elif bits_of(v) != bits:
+                bits = width_of(v)
+            elif width_of(v) != bits and (bits in _MX or width_of(v) in _MX):
+                raise ValueError(f"client {i} key {k!r}: {width_of(v)} codes in a round of {bits} uploads (a round's "
+                                 "uploads are all of one format: integer codes of one width, mx4 or mx8)")
+            elif width_of(v) != bits:
                 raise ValueError(f"client {i} key {k!r}: {bits_of(v)}-bit codes in a round of {bits}-bit uploads "
                                  + ("(a round's uploads are all q8 or all q4)" if {bits, bits_of(v)} == {8, 4} else
                                     "(a round's uploads are all of one width: q8, q4 or q1)"))
-            if bits in _PACKED:
-                tag, per = _PACKED[bits]
+            if bits in _PACKED or bits in _MX:
+                tag, per, blk, sdt = (bits, _MX[bits], MX_BLOCK, np.uint8) if bits in _MX else (*_PACKED[bits], Q4_BLOCK, _F32)
                 q8, sc, d, shape = v.get(tag), v.get("scale"), v.get("delta"), v.get("shape")
-                if not (type(q8) is np.ndarray and type(sc) is np.ndarray and q8.dtype == np.uint8 and sc.dtype == _F32
+                if not (type(q8) is np.ndarray and type(sc) is np.ndarray and q8.dtype == np.uint8 and sc.dtype == sdt
                         and type(shape) is tuple and all(type(n) is int and n >= 0 for n in shape)
-                        and sum(t in v for t in ("q8", "q4", "q1")) == 1
+                        and sum(t in v for t in _TAGS) == 1
                         and q8.ndim == 1 and q8.shape[0] == (math.prod(shape) + per - 1) // per and sc.ndim == 1
-                        and sc.shape[0] == n_blocks(math.prod(shape), Q4_BLOCK) and type(v.get("block")) is int
-                        and v["block"] == Q4_BLOCK and type(d) is bool and q8.flags.c_contiguous and sc.flags.c_contiguous):
+                        and sc.shape[0] == n_blocks(math.prod(shape), blk) and type(v.get("block")) is int
+                        and v["block"] == blk and type(d) is bool and q8.flags.c_contiguous and sc.flags.c_contiguous):
                     q8, sc, d = check_entry(k, v, i)  # raises what is wrong, or hands back the packed bytes as host arrays
                     shape = entry_shape(v)
             else:

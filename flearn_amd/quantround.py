@@ -1,13 +1,15 @@
 """The quantized round of the engine, bound on Aggregator as `ensemble_quantized` (DESIGN.md
-sections 17, 18 and 21): uploads whose fp32 tensors are int8, int4 or 1-bit sign block-quantized
-entries (quant.py) are summed by ops.deq_fold_stack / ops.deq_fold_q4_stack / ops.deq_fold_q1_stack
+sections 17, 18, 21 and 22): uploads whose fp32 tensors are int8, int4, 1-bit sign or Microscaling
+(MXFP4 / MXFP8) block-quantized entries (quant.py) are summed by ops.deq_fold_stack /
+ops.deq_fold_q4_stack / ops.deq_fold_q1_stack / ops.deq_fold_mx_stack
 from a device stack of one byte, half a byte, or one bit per parameter — the codes are never expanded
 to fp32 in memory — and the round ends in the server step every round ends in
 (Aggregator._server_step).  The widths differ in their layout constants (_LAYOUT) and in how a key's
 codes are indexed; the round is one.
 
 Padding.  A key ends on a scale block's boundary and the row on a chunk's.  Padding columns hold code 0,
-and whole padding blocks scale 0.  For 8 and 4 bits code 0 is the value 0; a sign code has no zero, so
+and whole padding blocks scale 0 — a Microscaling round's hold the scale byte MX_MIN_EXP, a legal one, since
+byte 0 is not.  For 8 and 4 bits and for both Microscaling element types code 0 is the value 0; a sign code has no zero, so
 the padding columns inside a 1-bit key's last block hold +scale and their sums are not 0.  Nothing
 reads them: the server step's results and the server optimiser's state are copied out per segment
 (offset, numel), a fused update works column by column, and no launch of this round reduces across
@@ -16,6 +18,7 @@ columns.
 from __future__ import annotations
 
 import dataclasses
+import functools
 
 import numpy as np
 import torch
@@ -44,7 +47,15 @@ def _refuse(agg, server_opt) -> None:
 # stack's dtype, the staging buffers' tag, the device entry)
 _LAYOUT = {8: (quant.BLOCK, quant.BLOCK, 1, torch.int8, "q8", ops.deq_fold_stack),
            4: (quant.Q4_BLOCK, na.Q4_CHUNK, 2, torch.uint8, "q4", ops.deq_fold_q4_stack),
-           1: (quant.Q1_BLOCK, na.Q1_CHUNK, 8, torch.uint8, "q1", ops.deq_fold_q1_stack)}
+           1: (quant.Q1_BLOCK, na.Q1_CHUNK, 8, torch.uint8, "q1", ops.deq_fold_q1_stack),
+           "mx4": (quant.MX_BLOCK, na.MX_CHUNK, 2, torch.uint8, "mx4", functools.partial(ops.deq_fold_mx_stack, elem=na.MX_FP4)),
+           "mx8": (quant.MX_BLOCK, na.MX_CHUNK, 1, torch.uint8, "mx8", functools.partial(ops.deq_fold_mx_stack, elem=na.MX_FP8))}
+
+
+def _scale_layout(bits):
+    """(the scale stack's dtype, what a padding block's scale holds): fp32 zeros, or for a Microscaling
+    round E8M0 bytes and the smallest legal one."""
+    return (torch.uint8, quant.MX_MIN_EXP) if bits in ("mx4", "mx8") else (torch.float32, 0)
 
 
 def _stand_ins(w_local_lst, keys, qkeys, entries):
@@ -86,7 +97,9 @@ def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, d
     """Clients [lo, hi) as one pinned int8 [K, stride] code stack and one fp32 [K, stride / 1024] scale
     stack on the device — for 4-bit codes uint8 [K, stride / 2], a key's packed bytes copied as they
     are to byte offset / 2, and scales [K, stride / 128]; 1-bit codes the same with eight columns per
-    byte (a key starts on a multiple of 128 columns: a whole byte); padding is code 0 with scale 0.  Rows are
+    byte (a key starts on a multiple of 128 columns: a whole byte); padding is code 0 with scale 0.  A
+    Microscaling round ("mx4" / "mx8") has blocks of 32, two or one columns per byte and a uint8 scale stack
+    [K, stride / 32] whose padding is the byte MX_MIN_EXP.  Rows are
     packed in groups (the packer's threads, one row range each) and every group's H2D is queued while
     the next is packed.  Returns the two device tensors."""
     block, _, per_byte, dtype, tag, _ = _LAYOUT[bits]
@@ -94,7 +107,8 @@ def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, d
     nb = stride // block
     pk = agg.packer
     hq = pk._staging((tag, slot), (k, stride // per_byte), dtype)
-    hs = pk._staging((tag + "s", slot), (k, nb), torch.float32)
+    sdtype, spad = _scale_layout(bits)
+    hs = pk._staging((tag + "s", slot), (k, nb), sdtype)
     nq, ns = hq.numpy(), hs.numpy()
     segs = [(s.key, s.offset, s.numel, s.offset // block, quant.n_blocks(s.numel, block),
              s.offset + padded_span(s.numel, block)) for s in g32.segments]
@@ -105,7 +119,7 @@ def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, d
     clean = pk.__dict__.setdefault("_q8_clean", {})
     if clean.get((tag, slot)) != sig:
         nq[...] = 0
-        ns[...] = 0
+        ns[...] = spad
         clean[(tag, slot)] = sig
 
     def rows(r0, r1):
@@ -120,7 +134,7 @@ def _pack_chunk(agg, g32: Group, entries, scales, lo: int, hi: int, slot: int, d
                     ns[r, b0 : b0 + b] = e[key][1]
 
     dq = pk.device_bucket((tag, slot), (k, stride // per_byte), dtype, device)
-    ds = pk.device_bucket((tag + "s", slot), (k, nb), torch.float32, device)
+    ds = pk.device_bucket((tag + "s", slot), (k, nb), sdtype, device)
     threaded = k > 1 and pk.workers > 1 and k * stride // per_byte >= SMALL_BYTES
     group = 2 * pk.workers if threaded else k
     for g0 in range(0, k, group):
@@ -146,7 +160,9 @@ def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_op
     2048 columns, a uint8 [N, stride / 2] stack, scales [N, stride / 128] and ops.deq_fold_q4_stack,
     and its audit carries "bits": 4 (an int8 round's audit is as it was: last_quant.get("bits", 8)); a
     round of 1-bit uploads has the same segments and stride, a uint8 [N, stride / 8] stack,
-    ops.deq_fold_q1_stack and "bits": 1.
+    ops.deq_fold_q1_stack and "bits": 1; a Microscaling round has segments on 32-column boundaries, the same
+    stride, a uint8 [N, stride / 2] (MXFP4) or [N, stride] (MXFP8) stack, uint8 scales [N, stride / 32],
+    ops.deq_fold_mx_stack, and "bits": 4 or 8 with "format": "mx".
 
     The round is planned with the plan's own numerics (make_plan over zero-strided fp32 stand-ins of
     the quantized keys), its fp32 group re-laid with segments on 1024-column boundaries; the codes are
@@ -207,8 +223,10 @@ def ensemble_quantized(agg, agg_weight_lst, w_local_lst, key_lst=None, server_op
             # the whole stride in one launch: padding columns hold sums nobody reads
             deq_fold(dq, ds, weights[lo:hi], acc if lo else None, acc, center=row, n_clients=hi - lo)
     nb = g32.stride // block
-    agg.last_quant = {"bytes_in": n * g32.stride // per_byte + 4 * n * nb, "bytes_fp32": 4 * n * base.groups[KIND_F32].stride,
-                      "delta": delta, "blocks": n * nb, **({"bits": bits} if bits != 8 else {})}
+    mx = bits in ("mx4", "mx8")
+    agg.last_quant = {"bytes_in": n * g32.stride // per_byte + (1 if mx else 4) * n * nb,
+                      "bytes_fp32": 4 * n * base.groups[KIND_F32].stride, "delta": delta, "blocks": n * nb,
+                      **({"bits": 8 // per_byte, "format": "mx"} if mx else {"bits": bits} if bits != 8 else {})}
     sums = {KIND_F32: [(packer.shards(plan, KIND_F32)[0], ops.FoldedSum(acc, na.ACC_F32, n, g32.stride))]}
     for kind, parts in stacks8.items():
         sums[kind] = parts

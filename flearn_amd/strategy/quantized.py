@@ -1,4 +1,4 @@
-"""FedAVG over int8, int4 or 1-bit block-quantized uploads (quant.py, quantround.py; DESIGN.md sections 17, 18, 21)."""
+"""FedAVG over int8, int4, 1-bit or Microscaling block-quantized uploads (quant.py, quantround.py; DESIGN.md sections 17, 18, 21, 22)."""
 from __future__ import annotations
 
 import numpy as np
@@ -43,18 +43,25 @@ class QuantizedAVG(AVG):
     compression is biased and does not converge alone, so error_feedback (EF-signSGD, Karimireddy et al.
     2019; the default for bits=1 and refused for the other widths) has the client instance keep the fp32
     residual e of its last upload: it quantizes x + e (the update x + e - g when delta is on) and sets e
-    to what it quantized minus what the server will read.  The server's work is the same."""
+    to what it quantized minus what the server will read.  The server's work is the same.
+    format="mx" (`setup_strategy("avg_mx4")`, `"avg_mx8"`): OCP Microscaling uploads, MXFP4 for bits=4 and
+    MXFP8 for bits=8 — E2M1 / E4M3 codes with one power-of-two scale byte per 32, 4.25 / 8.25 bits per
+    parameter, decoded on the device by gfx950's scaled converts; bits=1, stochastic
+    and error_feedback are refused with it.  format="int", the default, is everything above."""
 
     def __init__(self, server_opt=None, delta=True, stochastic=False, seed=None, encrypt=None, output="reference",
-                 device=None, chunk_clients=None, bits=8, error_feedback=None):
+                 device=None, chunk_clients=None, bits=8, error_feedback=None, format="int"):
         if isinstance(bits, bool) or bits not in (8, 4, 1):
             raise ValueError(f"bits must be 8, 4 or 1, got {bits!r}")
+        if quant._check_format(bits, format) and (stochastic or error_feedback):
+            raise ValueError('stochastic rounding and error_feedback are not implemented for format="mx"')
         if error_feedback not in (None, False, True) or (error_feedback and bits != 1):
             raise ValueError(f"error_feedback is bits=1's (True, False or None), got {error_feedback!r} with bits={bits!r}")
         if bits == 1 and stochastic:
             raise ValueError("stochastic rounding is not defined for bits=1")
         super().__init__(encrypt, output, device, None, None, chunk_clients)
         self.bits = int(bits)
+        self.format = format
         self.error_feedback = bits == 1 and error_feedback is not False
         self._residual = {}  # the client's: key -> what its last upload quantized minus its dequantized value
         self.server_opt = server_opt
@@ -78,7 +85,7 @@ class QuantizedAVG(AVG):
         sd = convert_to_np(trainer.weight)
         if self.error_feedback:
             return {"agg_weight": agg_weight, "params": self._quantize_with_feedback(sd, center)}
-        params = quant.quantize_state_dict(sd, center, self.stochastic, self._rng, self.bits)
+        params = quant.quantize_state_dict(sd, center, self.stochastic, self._rng, self.bits, self.format)
         return {"agg_weight": agg_weight, "params": params}
 
     def _quantize_with_feedback(self, sd, center):

@@ -25,7 +25,7 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
     server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
     server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes; "avg_q1": 1-bit sign codes,
-    stochastic refused, and error_feedback),
+    stochastic refused, and error_feedback; "avg_mx4" / "avg_mx8": Microscaling MXFP4 / MXFP8 codes, stochastic refused),
     server_opt, stochastic and seed (BF16AVG, "avg_bf16")."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
@@ -68,6 +68,9 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
             strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False), strategy_p.get("seed"),
             **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}, bits=1,
             error_feedback=strategy_p.get("error_feedback")),
+        **{f"avg_mx{b}": (lambda b=b: QuantizedAVG(
+            strategy_p.get("server_opt"), strategy_p.get("delta", True), strategy_p.get("stochastic", False), strategy_p.get("seed"),
+            **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}, bits=b, format="mx")) for b in (4, 8)},
         "avg_bf16": lambda: BF16AVG(
             strategy_p.get("server_opt"), strategy_p.get("stochastic", False), strategy_p.get("seed"),
             **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}),

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 27
+#define FA_ABI_VERSION 28
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 / fa_deq_fold_q1 call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 / fa_deq_fold_q1 / fa_deq_fold_mx call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -606,6 +606,49 @@ int fa_deq_fold_q1(const uint8_t* stack, int64_t row_stride, int32_t n_clients, 
                    int64_t scale_stride, const float* weights, const float* center,
                    const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
                    void* stream);
+
+/* ---- Microscaling uploads: MXFP4 and MXFP8 (ABI 28) -----------------------
+ * OCP Microscaling v1.0 rows: one element code per column and one E8M0 scale byte e per FA_MX_BLOCK
+ * columns of the row (block b covers columns [32 b, 32 b + 32)), standing for 2^(e - 127).  elem =
+ * FA_MX_FP4: E2M1 codes (sign, two exponent bits, one mantissa bit: +-0, 0.5, 1, 1.5, 2, 3, 4, 6, no
+ * inf, no NaN), two per byte — column c is a nibble of byte c / 2, the low one for even c.  elem =
+ * FA_MX_FP8: E4M3 "fn" codes (bias 7, maximum 448, subnormals down to 2^-9, no inf, S.1111.111 is
+ * NaN), one per byte.  A legal scale byte is FA_MX_MIN_EXP ... FA_MX_MAX_EXP (2^-100 ... 2^100):
+ * every decoded value is then zero or an fp32 normal, and exact.  What any other scale byte gives
+ * (255, E8M0's NaN, included) is unspecified, and the Python side refuses it.  There is no reference
+ * counterpart.  fa_deq_fold_mx is fa_deq_fold_q4 for such rows.  Per column c of the window and row
+ * i, every operation rounded to fp32 and none contracted:
+ *   x   = decode(code of column col_begin + c of row i)
+ *         * 2^(scales[i * scale_stride + (col_begin + c) / 32] - 127)                         (exact)
+ *   x   = fl32(center[col_begin + c] + x)                      when center != NULL (delta uploads)
+ *   acc = fl32(acc + fl32(weights[i] * x))                     in list order
+ * acc starts from acc_in[c]; acc_in == NULL opens the round: acc = fl32(weights[0] * x_0), the other
+ * rows added — fa_fold's (FA_ACC_F32) bits on the dequantized rows, -0.0 (a code of sign bit alone
+ * is -0.0) and overflow to inf included; an E4M3 NaN code gives a NaN sum, and only a NaN's bits are
+ * free.  Columns are elements: row_stride is in BYTES, so a row holds 2 * row_stride (FP4) or
+ * row_stride (FP8) columns; scale_stride is in bytes per client row; center is indexed by absolute
+ * column, acc_in / acc_out from 0 at col_begin.  acc_out may be acc_in.  Weights and scales are read
+ * from device memory per row: no client cap.
+ * FA_ERR_ARG: a NULL stack / scales / weights / acc_out, n_clients < 1, an elem other than
+ * FA_MX_FP4 / FA_MX_FP8, n_cols < 0, a window outside the row or whose last block is past
+ * scale_stride, or acc_in overlapping acc_out within n_cols elements without equalling it.
+ * FA_ERR_ALIGN: stack / center / acc_in / acc_out not 16-byte aligned, row_stride no multiple of 16,
+ * col_begin no multiple of FA_MX_CHUNK (one wave's 32 columns per lane: 2048 columns), scales /
+ * weights not 4-byte aligned, scale_stride no multiple of 4.  Every error is decided before any HIP
+ * call.  n_cols == 0 is a no-op that launches nothing.  Code rows are read through a range rounded up
+ * to 4 bytes (inside the row); nothing outside acc_out[0, n_cols) is written.  fa_set_reduce_grid
+ * applies; fa_last_launch names the instantiation, "mx_fold_kernel<4,1,8,4,true>" (the first
+ * argument is elem), launches = 1.                                                               */
+#define FA_MX_BLOCK 32
+#define FA_MX_CHUNK 2048
+#define FA_MX_FP4 4
+#define FA_MX_FP8 8
+#define FA_MX_MIN_EXP 27
+#define FA_MX_MAX_EXP 227
+int fa_deq_fold_mx(const uint8_t* stack, int64_t row_stride, int32_t n_clients, const uint8_t* scales,
+                   int64_t scale_stride, const float* weights, const float* center,
+                   const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
+                   int32_t elem, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

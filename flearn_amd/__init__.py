@@ -10,7 +10,7 @@ The hot path (Strategy.server -> server_ensemble) runs hand-written HIP kernels 
 through the C ABI in include/flearn_amd.h; there is no CPU fallback.
 """
 from .strategy import (AVG, AVGM, BF16AVG, BN, LG, LG_R, OPT, SGD, BaseEncrypt, Distill, Dyn, Krum, Median, MultiKrum, NormClip,
-                       ParentStrategy, Prox, QuantizedAVG, StreamedNormClip, Strategy, TrimmedMean)
+                       ParentStrategy, Prox, QuantizedAVG, StreamedNormClip, Strategy, TopKAVG, TrimmedMean)
 from .strategy import convert_to_np, convert_to_tensor
 from .utils import base_strategy_lst, setup_seed, setup_strategy
 from .wire import Encrypt
@@ -37,6 +37,7 @@ __all__ = [
     "StreamedNormClip",
     "QuantizedAVG",
     "BF16AVG",
+    "TopKAVG",
     "Strategy",
     "ParentStrategy",
     "BaseEncrypt",

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 28
+ABI_VERSION = 29
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -39,6 +39,8 @@ Q1_BLOCK, Q1_CHUNK = 128, 2048  # of a 1-bit sign row, and fa_deq_fold_q1's col_
 MX_BLOCK, MX_CHUNK = 32, 2048  # of a Microscaling row, and fa_deq_fold_mx's col_begin unit (FA_MX_BLOCK, FA_MX_CHUNK)
 MX_FP4, MX_FP8 = 4, 8  # fa_deq_fold_mx's element types (FA_MX_FP4, FA_MX_FP8)
 MX_MIN_EXP, MX_MAX_EXP = 27, 227  # the legal E8M0 scale bytes (FA_MX_MIN_EXP, FA_MX_MAX_EXP)
+SPARSE_MAX_CLIENTS, SPARSE_WINDOW = 1024, 4096  # fa_sparse_fold_f32's rows per launch and columns per wave (FA_SPARSE_MAX_CLIENTS, FA_SPARSE_WINDOW)
+SPARSE_PAD = 0xFFFFFFFF  # the column of a padding pair
 CLIP_MAX_CLIENTS = 128  # fa_rownorm2_f32's and fa_clip_sum_f32's (FA_CLIP_MAX_CLIENTS)
 OP_BY_NAME = {"mean": OP_MEAN, "avgm": OP_AVGM, "adagrad": OP_ADAGRAD, "yogi": OP_YOGI, "adam": OP_ADAM, "dyn": OP_DYN}
 
@@ -89,6 +91,8 @@ EXPORTS = (
     "fa_fold_bf16",
     "fa_deq_fold_q1",
     "fa_deq_fold_mx",
+    "fa_sparse_workspace",
+    "fa_sparse_fold_f32",
     "fa_b64_decoded_size",
     "fa_b64_decode",
     "fa_b64_decode_ranges",
@@ -274,6 +278,8 @@ def load(require_gpu: bool = False):
                 "fa_fold_bf16": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_deq_fold_q1": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, P], ctypes.c_int),
                 "fa_deq_fold_mx": ([P, I64, I32, P, I64, P, P, P, P, I64, I64, I32, P], ctypes.c_int),
+                "fa_sparse_workspace": ([I32, I64], I64),
+                "fa_sparse_fold_f32": ([P, I64, I32, P, P, ctypes.c_float, P, P, I64, I64, P, I64, P], ctypes.c_int),
                 "fa_b64_decoded_size": ([P, I64], I64),
                 "fa_b64_decode": ([P, I64, P, I64, I32], ctypes.c_int),
                 "fa_b64_decode_ranges": ([P, I64, I32, P, P, P, I32], ctypes.c_int),

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as na
-from . import bf16round, clipstream, quantround, robustround, smallround
+from . import bf16round, clipstream, quantround, robustround, smallround, sparseround
 from .bucketplan import BucketPlan, Shard, key_runs, make_plan, rank_width, select_keys  # noqa: F401
 from .dist import gather_columns
 from .ops import (FoldedSum, StackSum, _byte_range, _check_arrays, _check_cuda, _check_stack, _check_v_out,  # noqa: F401
@@ -93,6 +93,9 @@ class Aggregator:
     #: refusing bfloat16 tensors
     ensemble_bf16 = bf16round.ensemble_bf16
     last_bf16 = None
+    #: the round of top-k sparse uploads (sparseround.py); last_sparse: its audit
+    ensemble_sparse = sparseround.ensemble_sparse
+    last_sparse = None
 
     def __init__(self, device=None, output: str = "reference", workers: int = 8, devices=None, group=None,
                  reorder: bool = False, chunk_clients: int | None = None):

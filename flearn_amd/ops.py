@@ -551,6 +551,70 @@ def _deq_fold(entry, what, dtype, per_byte, block, stack, scales, weights, acc_i
     na.check(rc, entry)
 
 
+def sparse_workspace(n_clients: int, n_cols: int) -> int:
+    """Bytes of workspace sparse_fold_stack needs (fa_sparse_workspace; a host function)."""
+    need = na.load().fa_sparse_workspace(n_clients, n_cols)
+    if need < 0:
+        na.check(int(need), "fa_sparse_workspace")
+    return int(need)
+
+
+def sparse_fold_stack(pairs: torch.Tensor, weights: torch.Tensor, acc_in, acc_out: torch.Tensor, *,
+                      center: torch.Tensor | None = None, wsum: float = 0.0, n_clients: int | None = None,
+                      col_begin: int = 0, n_cols: int | None = None, workspace: torch.Tensor | None = None) -> None:
+    """One chunk of top-k sparse client rows added to an fp32 accumulator (fa_sparse_fold_f32; DESIGN.md
+    section 23, restated by tests/sparse_ref.py), queued on torch's current stream.  pairs: int32 or
+    uint32 [N, kstride, 2] on the device, kstride even: row i's (column of the bucket, bit pattern of the
+    fp32 value) pairs, columns strictly ascending, padded with (na.SPARSE_PAD, 0).  Per column c of the
+    window [col_begin, +n_cols) (n_cols None: acc_out's length): acc = acc_in[c], or — acc_in None, the
+    chunk opens the round — fl32(wsum * center[col_begin + c]), or +0.0 without a centre; then for the rows
+    in list order that hold a pair (col_begin + c, v): acc = fl32(acc + fl32(weights[i] * v)).  center (an
+    fp32 device row laid out like a bucket row) is read by the opening chunk only.  acc_out may be acc_in;
+    fold_finish divides it (na.ACC_F32).  At most na.SPARSE_MAX_CLIENTS rows; col_begin a multiple of 4.
+    workspace: a 16-B aligned device buffer of at least sparse_workspace(N, n_cols) bytes (else a fresh
+    one)."""
+    if (not isinstance(pairs, torch.Tensor) or pairs.dim() != 3 or pairs.shape[2] != 2 or not pairs.is_cuda
+            or pairs.stride(2) != 1 or pairs.stride(1) != 2):
+        raise ValueError("pairs must be a 3-D [N, kstride, 2] device tensor with contiguous rows")
+    if pairs.dtype not in (torch.int32, torch.uint32):
+        raise TypeError(f"pairs must be torch.int32 or torch.uint32, got {pairs.dtype}")
+    dev = pairs.device
+    n = pairs.shape[0] if n_clients is None else n_clients
+    if not 1 <= n <= pairs.shape[0]:
+        raise ValueError("n_clients out of range")
+    if n > na.SPARSE_MAX_CLIENTS:
+        raise ValueError(f"at most {na.SPARSE_MAX_CLIENTS} rows per call, got {n}")
+    if (not isinstance(acc_out, torch.Tensor) or acc_out.dtype != torch.float32 or acc_out.device != dev
+            or not acc_out.is_contiguous()):
+        raise ValueError("acc_out must be a contiguous torch.float32 tensor on the pairs' device")
+    ncols = acc_out.numel() if n_cols is None else n_cols
+    if col_begin < 0 or ncols < 0:
+        raise ValueError("column window out of range")
+    if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.device != dev
+            or not weights.is_contiguous() or weights.numel() < n):
+        raise ValueError(f"weights must be a contiguous torch.float32 tensor of at least {n} elements on the pairs' device")
+    if center is not None:
+        _check_center_row(center, pairs, col_begin + ncols)
+    for name, t in (("acc_in", acc_in), ("acc_out", acc_out)):
+        if name == "acc_in" and t is None:
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() < ncols or not t.is_contiguous()
+                or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous torch.float32 tensor of at least {ncols} elements on the "
+                             "pairs' device")
+    need = sparse_workspace(n, ncols)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous()
+          or workspace.numel() * workspace.element_size() < need):
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on the pairs' device")
+    rc = na.lib().fa_sparse_fold_f32(pairs.data_ptr(), pairs.stride(0) // 2, n, weights.data_ptr(), _ptr(center),
+                                     float(wsum), _ptr(acc_in), acc_out.data_ptr(), col_begin, ncols,
+                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                     na.stream_handle(dev))
+    na.check(rc, "fa_sparse_fold_f32")
+
+
 _BF16_STACK_DTYPES = (torch.bfloat16, torch.int16, torch.uint16)
 
 

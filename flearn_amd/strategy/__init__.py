@@ -2,7 +2,7 @@
 
 In scope (server reduce on the MI355X engine): AVG, AVGM, OPT, SGD, Prox, BN, LG, LG_R, Dyn,
 Distill; and, beyond the reference, the robust rules TrimmedMean, Median, Krum, MultiKrum and
-NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 or int4 block-quantized uploads) and BF16AVG (bf16.py: bfloat16 uploads).  Out of scope (server-side model training): DF, MD, PAV — not
+NormClip and StreamedNormClip (robust.py), and QuantizedAVG (quantized.py: int8 or int4 block-quantized uploads) and BF16AVG (bf16.py: bfloat16 uploads) and TopKAVG (sparse.py: top-k sparse uploads).  Out of scope (server-side model training): DF, MD, PAV — not
 provided; keep using flearn's for those.
 """
 from .avg import AVG
@@ -18,6 +18,7 @@ from .prox import Prox
 from .quantized import QuantizedAVG
 from .robust import Krum, Median, MultiKrum, NormClip, StreamedNormClip, TrimmedMean
 from .sgd import SGD
+from .sparse import TopKAVG
 from .strategy import BaseEncrypt, ParentStrategy, Strategy
 from .utils import convert_to_np, convert_to_tensor
 
@@ -40,6 +41,7 @@ __all__ = [
     "StreamedNormClip",
     "QuantizedAVG",
     "BF16AVG",
+    "TopKAVG",
     "ParentStrategy",
     "Strategy",
     "BaseEncrypt",

@@ -6,7 +6,7 @@ import random
 import numpy as np
 import torch
 
-from .strategy import AVG, AVGM, BF16AVG, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, NormClip, Prox, QuantizedAVG, StreamedNormClip, TrimmedMean
+from .strategy import AVG, AVGM, BF16AVG, BN, LG, LG_R, OPT, SGD, Distill, Dyn, Krum, Median, MultiKrum, NormClip, Prox, QuantizedAVG, StreamedNormClip, TopKAVG, TrimmedMean
 
 __all__ = ["setup_strategy", "setup_seed", "base_strategy_lst", "OUT_OF_SCOPE"]
 
@@ -26,7 +26,8 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
     server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes; "avg_q1": 1-bit sign codes,
     stochastic refused, and error_feedback; "avg_mx4" / "avg_mx8": Microscaling MXFP4 / MXFP8 codes, stochastic refused),
-    server_opt, stochastic and seed (BF16AVG, "avg_bf16")."""
+    server_opt, stochastic and seed (BF16AVG, "avg_bf16"), server_opt, ratio, k, delta and error_feedback (TopKAVG,
+    "avg_topk": top-k sparse uploads)."""
     shared_key_layers = strategy_p.get("shared_key_layers", None)
     eng = {k: strategy_p[k] for k in ("output", "device", "devices", "group", "chunk_clients") if k in strategy_p}
     server_side = strategy_p.get("server_side", False)
@@ -73,6 +74,10 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
             **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}, bits=b, format="mx")) for b in (4, 8)},
         "avg_bf16": lambda: BF16AVG(
             strategy_p.get("server_opt"), strategy_p.get("stochastic", False), strategy_p.get("seed"),
+            **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}),
+        "avg_topk": lambda: TopKAVG(
+            strategy_p.get("server_opt"), strategy_p.get("ratio", 0.01), strategy_p.get("k"), strategy_p.get("delta", True),
+            strategy_p.get("error_feedback", True),
             **{k: v for k, v in eng.items() if k in ("output", "device", "chunk_clients")}),
     }
     if name in factories:

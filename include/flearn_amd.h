@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 28
+#define FA_ABI_VERSION 29
 
 /* return codes */
 #define FA_OK 0
@@ -275,7 +275,7 @@ int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
  * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_rownorm2_f32 /
- * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 / fa_deq_fold_q1 / fa_deq_fold_mx call launched.  For tests and profilers that must know which kernel instantiation a
+ * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 / fa_deq_fold_q1 / fa_deq_fold_mx / fa_sparse_fold_f32 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
  * pointer and two integers.  No reference counterpart.  ABI 16.
@@ -649,6 +649,40 @@ int fa_deq_fold_mx(const uint8_t* stack, int64_t row_stride, int32_t n_clients, 
                    int64_t scale_stride, const float* weights, const float* center,
                    const float* acc_in, float* acc_out, int64_t col_begin, int64_t n_cols,
                    int32_t elem, void* stream);
+
+/* ---- top-k sparse uploads -----------------------------------------------
+ * A client sends the k largest-magnitude coordinates of its update (Aji & Heafield 2017; Lin et al.
+ * 2018; Stich et al. 2018; Sattler et al. 2019) and the server's work scales with the pairs, not with
+ * N x P.  There is no reference counterpart.  ABI 29.
+ * pairs: uint32 [n_clients][row_stride_pairs][2], a pair being (column of the bucket, bit pattern of
+ * the fp32 value); a row's columns are strictly ascending and the row is padded to row_stride_pairs
+ * with (0xFFFFFFFF, 0).  Per column c of the window [col_begin, +n_cols):
+ *   acc = acc_in[c], or (acc_in NULL: the call opens the round) fl32(wsum * center[col_begin + c]),
+ *   or (center NULL too) +0.0; then for the rows i in list order that hold a pair (col_begin + c, v):
+ *   acc = fl32(acc + fl32(weights[i] * v)); acc_out[c] = acc.
+ * No fused multiply-add.  center is read only when acc_in is NULL: it enters a round once, not once
+ * per row, so a delta round's bits are this rule's and not the dense fold's of the densified rows;
+ * without a centre, and with finite weights >= 0, they are the dense fold's.  Rows chained through
+ * acc_in leave the bits of one call over all rows.  acc_out may be acc_in.  Two launches: a binary
+ * search of every row for every window boundary (int32 [n][windows + 1] in `workspace`), then one
+ * wave per window of FA_SPARSE_WINDOW columns, its sums in LDS.  A pair outside its row's segment or
+ * its window is not acted on: columns that are not ascending give a meaningless sum, never an access
+ * outside the arrays.  FA_ERR_ARG: a null pairs / weights / acc_out / workspace, n_clients outside
+ * [1, FA_SPARSE_MAX_CLIENTS], a negative size, acc_out overlapping acc_in without being it;
+ * FA_ERR_SIZE: col_begin + n_cols > 2^32 - 1, row_stride_pairs > 2^27, workspace_bytes <
+ * fa_sparse_workspace; FA_ERR_ALIGN: pairs, center, acc_in, acc_out or workspace not 16-byte aligned,
+ * row_stride_pairs odd, col_begin no multiple of 4.  Every error is decided before any HIP call.
+ * fa_set_reduce_grid applies to the second launch; fa_last_launch names it,
+ * "window_fold_kernel<4096,8,4>" (window, rows in flight, waves per block), launches = 2. */
+#define FA_SPARSE_MAX_CLIENTS 1024
+#define FA_SPARSE_WINDOW 4096
+/* Bytes of workspace fa_sparse_fold_f32 needs for this shape; FA_ERR_ARG for n_clients outside
+ * [1, FA_SPARSE_MAX_CLIENTS] or n_cols outside [0, 2^32 - 1].  HOST function, no HIP call.        */
+int64_t fa_sparse_workspace(int32_t n_clients, int64_t n_cols);
+int fa_sparse_fold_f32(const uint32_t* pairs, int64_t row_stride_pairs, int32_t n_clients,
+                       const float* weights, const float* center, float wsum, const float* acc_in,
+                       float* acc_out, int64_t col_begin, int64_t n_cols, void* workspace,
+                       int64_t workspace_bytes, void* stream);
 
 /* Copy nbytes from src to dst with a kernel on `stream` (both 16-byte aligned; either may be
  * pinned host memory mapped into the GPU's address space).  For a device result going to a

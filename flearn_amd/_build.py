@@ -10,7 +10,7 @@ from pathlib import Path
 HERE = Path(__file__).resolve().parent
 REPO = HERE.parent
 # the device units, one per entry group (each includes only the kernel families it launches)
-SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport", "fa_gram", "fa_clip", "fa_noise", "fa_quant", "fa_quant4", "fa_bf16", "fa_trimwide", "fa_quant1", "fa_mx", "fa_sparse")]
+SOURCES = [HERE / "csrc" / f"{name}.hip" for name in ("fa_reduce", "fa_rows", "fa_transport", "fa_gram", "fa_clip", "fa_noise", "fa_quant", "fa_quant4", "fa_bf16", "fa_trimwide", "fa_quant1", "fa_mx", "fa_sparse", "fa_gramwide")]
 # flags of single units, after the common ones.  fa_quant4 is built with packed fp32 operations off (cc1's target
 # feature, cleared): the build that ships is the one that was run, tested and measured.  The packed build of the same
 # source has only been compiled: it was never run, so it is neither checked against the unit's bit-exact tests nor

@@ -17,7 +17,7 @@ from pathlib import Path
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libflearn_amd.so"
-ABI_VERSION = 29
+ABI_VERSION = 30
 FENCE_RELEASE, FENCE_ACQUIRE = 0, 1  # fa_cache_fence kinds
 
 FA_OK = 0
@@ -33,6 +33,7 @@ ACC_F32, ACC_F32_W64, ACC_F64, ACC_I64 = 0, 1, 2, 3  # fa_fold accumulator kinds
 TRIM_MAX_CLIENTS = 128  # fa_trim_sum's deepest client stack (FA_TRIM_MAX_CLIENTS)
 TRIM_WIDE_MAX_CLIENTS = 1024  # fa_trim_sum_wide's (FA_TRIM_WIDE_MAX_CLIENTS)
 GRAM_MAX_CLIENTS = 128  # fa_gram_f32's (FA_GRAM_MAX_CLIENTS)
+GRAM_WIDE_MAX_CLIENTS = 1024  # fa_gram_f32_wide's (FA_GRAM_WIDE_MAX_CLIENTS)
 Q8_BLOCK = 1024  # columns per scale of a quantized row (FA_Q8_BLOCK)
 Q4_BLOCK, Q4_CHUNK = 128, 2048  # of a 4-bit quantized row, and fa_deq_fold_q4's col_begin unit (FA_Q4_BLOCK, FA_Q4_CHUNK)
 Q1_BLOCK, Q1_CHUNK = 128, 2048  # of a 1-bit sign row, and fa_deq_fold_q1's col_begin unit (FA_Q1_BLOCK, FA_Q1_CHUNK)
@@ -81,6 +82,8 @@ EXPORTS = (
     "fa_trim_sum_wide",
     "fa_gram_workspace",
     "fa_gram_f32",
+    "fa_gram_wide_workspace",
+    "fa_gram_f32_wide",
     "fa_rownorm_workspace",
     "fa_rownorm2_f32",
     "fa_clip_sum_f32",
@@ -268,6 +271,8 @@ def load(require_gpu: bool = False):
                 "fa_trim_sum_wide": ([I32, P, I64, I32, I32, P, I64, I64, P], ctypes.c_int),
                 "fa_gram_workspace": ([I32, I64], I64),
                 "fa_gram_f32": ([P, I64, I32, P, I64, I64, P, I64, P, P], ctypes.c_int),
+                "fa_gram_wide_workspace": ([I32, I64], I64),
+                "fa_gram_f32_wide": ([P, I64, I32, P, I64, I64, P, I64, P, P], ctypes.c_int),
                 "fa_rownorm_workspace": ([I32, I64], I64),
                 "fa_rownorm2_f32": ([P, I64, I32, P, I64, I64, P, I64, P, P], ctypes.c_int),
                 "fa_clip_sum_f32": ([P, I64, I32, P, P, P, I64, I64, P], ctypes.c_int),

@@ -103,7 +103,7 @@ def ensemble_trimmed(agg, w_local_lst, trim: int, key_lst=None, server_opt: Serv
 
 # -- Krum / multi-Krum ---------------------------------------------------------------------------
 def ensemble_krum(agg, w_local_lst, f: int, m: int, key_lst=None, server_opt: ServerOptimizer | None = None,
-                  center=None):
+                  center=None, wide: bool = False):
     """Multi-Krum (Blanchard et al., NeurIPS 2017; Krum is m = 1): the m uploads closest to their
     N - f - 2 nearest neighbours are averaged, the others are left out whole, and `last_krum`
     says which.  The uploads are planned (make_plan for Python-int weights) and packed as ever
@@ -125,9 +125,16 @@ def ensemble_krum(agg, w_local_lst, f: int, m: int, key_lst=None, server_opt: Se
     Refused before anything is queued: float16 buckets and FedDyn state (TypeError); several
     devices, group=, chunk_clients, more than 128 clients, bad f / m, and uploads without an
     fp32 bucket to measure distances on (ValueError).  More than f non-finite uploads: ValueError
-    after the Gram."""
+    after the Gram.
+
+    wide=True takes up to 1024 clients (fa_gram_f32_wide: past 128 the Gram is made per pair of
+    128-row panels and column slice, O(N^2 d) products).  Everything else is the same round."""
     _refuse(agg, server_opt)
-    plan = _plan_unit_weights(w_local_lst, key_lst, na.GRAM_MAX_CLIENTS, "Krum")
+    if wide:
+        plan = _plan_unit_weights(w_local_lst, key_lst, na.GRAM_WIDE_MAX_CLIENTS, "Krum")
+    else:
+        plan = _plan_unit_weights(w_local_lst, key_lst, na.GRAM_MAX_CLIENTS, "Krum",
+                                  f" (wide=True takes {na.GRAM_WIDE_MAX_CLIENTS})")
     n = plan.n_clients
     f, m = krum.check_counts(n, f, m)
     g32 = plan.groups.get(KIND_F32)
@@ -138,7 +145,7 @@ def ensemble_krum(agg, w_local_lst, f: int, m: int, key_lst=None, server_opt: Se
     agg.last_krum = None
     stacks = agg.packer.pack(plan, w_local_lst)
     dense = {kind: agg.packer.dense_stack(plan, kind, parts, n) for kind, parts in stacks.items()}
-    gram = client_gram(agg, plan, dense, centre)
+    gram = client_gram(agg, plan, dense, centre, wide)
     # (a slab, the caller's memory read in place, needs no hold for the Gram launches: client_gram's
     # copy to the host has waited for them; the selected rows' reduce keeps it through its row table)
     selected, scores = krum.krum_select(gram, f, m)
@@ -272,20 +279,21 @@ def client_norm2(agg, g32: Group, stack, row, n: int, device) -> np.ndarray:
     return norm2
 
 
-def client_gram(agg, plan: BucketPlan, dense: dict, centre):
+def client_gram(agg, plan: BucketPlan, dense: dict, centre, wide: bool = False):
     """The clients' float64 [N, N] Gram matrix of the fp32 bucket, on the host: one ops.gram_stack
-    launch per run of keys, `centre` (_check_center's pieces, or None) subtracted from every row,
-    and the one synchronisation of the round before its result."""
+    launch per run of keys (wide: fa_gram_f32_wide), `centre` (_check_center's pieces, or None)
+    subtracted from every row, and the one synchronisation of the round before its result."""
     g32, n = plan.groups[KIND_F32], plan.n_clients
     sh, stack = dense[KIND_F32]
     with torch.cuda.device(sh.device):
         row = _center_row(agg, g32, centre, sh.device)
         runs = key_runs(g32)
         grams = agg.packer.device_bucket(("gram", KIND_F32), (len(runs), n, n), torch.float64, sh.device)
-        work_bytes = max(ops.gram_workspace(n, c1 - c0) for c0, c1 in runs)
+        work_bytes = max(ops.gram_workspace(n, c1 - c0, wide) for c0, c1 in runs)
         work = agg.packer.device_bucket(("gram_work", KIND_F32), (work_bytes,), torch.uint8, sh.device)
         for i, (c0, c1) in enumerate(runs):
-            ops.gram_stack(stack, center=row, n_clients=n, col_begin=c0, n_cols=c1 - c0, out=grams[i], workspace=work)
+            ops.gram_stack(stack, center=row, n_clients=n, col_begin=c0, n_cols=c1 - c0, out=grams[i], workspace=work,
+                           wide=wide)
         host = grams.cpu().numpy()
     gram = host[0].copy()
     for part in host[1:]:  # partial Grams add: in key order, float64

@@ -107,13 +107,14 @@ class MultiKrum(_RobustRound):
     uncentred.  None never centres.  The centre is the server's own state, never a client's row.
     server_opt: a ServerOptimizer fused into the divide, as for TrimmedMean.  Distances are measured
     on the fp32 tensors only (int64 / float64 buffers such as BN counters do not enter them).  At
-    most 128 clients per round, one device; more than f non-finite uploads, like any client-data
-    error, take server_exception's route.  `agg_weight` is required and ignored: a client must not be
-    able to buy influence with its own weight."""
+    most 128 clients per round (wide=True: 1024, Aggregator.ensemble_krum), one device; more than f
+    non-finite uploads, like any client-data error, take server_exception's route.  `agg_weight` is
+    required and ignored: a client must not be able to buy influence with its own weight."""
 
     def __init__(self, f, m=None, server_opt=None, center="previous", encrypt=None, output="reference", device=None,
-                 devices=None, group=None, chunk_clients=None):
+                 devices=None, group=None, chunk_clients=None, wide=False):
         super().__init__(encrypt, output, device, devices, group, chunk_clients)
+        self.wide = bool(wide)
         self.f = self._check_count("f", f, 0)
         self.m = None if m is None else self._check_count("m", m, 1)
         if center is not None and center != "previous":
@@ -137,7 +138,7 @@ class MultiKrum(_RobustRound):
         by server_pre_processing and not used."""
         center = self._prev_glob if self.center == "previous" else None
         w_glob = self.engine.ensemble_krum(w_local_lst, self.f, self.select_count(len(w_local_lst)), key_lst,
-                                           server_opt=server_opt, center=center)
+                                           server_opt=server_opt, center=center, wide=self.wide)
         if self.center == "previous":  # a copy of its own: the caller may change what it is handed
             self._prev_glob = {k: v.detach().clone() if isinstance(v, torch.Tensor) else np.array(v)
                                for k, v in w_glob.items()}
@@ -146,11 +147,11 @@ class MultiKrum(_RobustRound):
 
 class Krum(MultiKrum):
     """Krum: the one upload of lowest score becomes the global model (MultiKrum with m = 1).
-    `agg_weight` is required and ignored."""
+    wide=True: up to 1024 clients, as for MultiKrum.  `agg_weight` is required and ignored."""
 
     def __init__(self, f, server_opt=None, center="previous", encrypt=None, output="reference", device=None,
-                 devices=None, group=None, chunk_clients=None):
-        super().__init__(f, 1, server_opt, center, encrypt, output, device, devices, group, chunk_clients)
+                 devices=None, group=None, chunk_clients=None, wide=False):
+        super().__init__(f, 1, server_opt, center, encrypt, output, device, devices, group, chunk_clients, wide)
 
 
 class NormClip(_RobustRound):

@@ -22,7 +22,7 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
     `custom_strategy`, else SystemError.  Extra keyword arguments understood here:
     shared_key_layers (LG / LG_R), h (Dyn), output / device / devices / group / chunk_clients
     (engine), server_side (AVGM / OPT), trim, server_opt and wide (TrimmedMean; Median: all but trim),
-    f, m, center and server_opt (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
+    f, m, center, server_opt and wide (Krum / MultiKrum; f defaults to 0), tau, quantile, center,
     server_opt, noise_multiplier, seed and sequence (NormClip; StreamedNormClip: all but quantile),
     server_opt, delta, stochastic and seed (QuantizedAVG, "avg_q8"; "avg_q4": the same with 4-bit codes; "avg_q1": 1-bit sign codes,
     stochastic refused, and error_feedback; "avg_mx4" / "avg_mx8": Microscaling MXFP4 / MXFP8 codes, stochastic refused),
@@ -47,9 +47,10 @@ def setup_strategy(strategy_name, custom_strategy, **strategy_p):
         "trimmedmean": lambda: TrimmedMean(strategy_p.get("trim", 0.1), strategy_p.get("server_opt"), **eng,
                                              wide=strategy_p.get("wide", False)),
         "median": lambda: Median(strategy_p.get("server_opt"), **eng, wide=strategy_p.get("wide", False)),
-        "krum": lambda: Krum(strategy_p.get("f", 0), strategy_p.get("server_opt"), strategy_p.get("center", "previous"), **eng),
+        "krum": lambda: Krum(strategy_p.get("f", 0), strategy_p.get("server_opt"), strategy_p.get("center", "previous"), **eng,
+                             wide=strategy_p.get("wide", False)),
         "multikrum": lambda: MultiKrum(strategy_p.get("f", 0), strategy_p.get("m"), strategy_p.get("server_opt"),
-                                       strategy_p.get("center", "previous"), **eng),
+                                       strategy_p.get("center", "previous"), **eng, wide=strategy_p.get("wide", False)),
         "normclip": lambda: NormClip(strategy_p.get("tau"), strategy_p.get("quantile"), strategy_p.get("server_opt"),
                                      strategy_p.get("center", "previous"), **eng,
                                      noise_multiplier=strategy_p.get("noise_multiplier"), seed=strategy_p.get("seed"),

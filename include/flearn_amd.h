@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 29
+#define FA_ABI_VERSION 30
 
 /* return codes */
 #define FA_OK 0
@@ -274,7 +274,7 @@ int fa_set_reduce_grid(int32_t grid);
 int fa_reduce_windows(int32_t op, int64_t n_cols);
 
 /* HOST function: what the calling thread's last fa_reduce_f32 / _f32_splitn / _f32_rows / _f64 /
- * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_rownorm2_f32 /
+ * _i64 / _f16 / fa_fold / fa_fold_finish / fa_trim_sum / fa_trim_sum_wide / fa_gram_f32 / fa_gram_f32_wide / fa_rownorm2_f32 /
  * fa_clip_sum_f32 / fa_clip_fold_f32 / fa_gauss_add_f32 / fa_deq_fold_q8 / fa_deq_fold_q4 / fa_fold_bf16 / fa_deq_fold_q1 / fa_deq_fold_mx / fa_sparse_fold_f32 call launched.  For tests and profilers that must know which kernel instantiation a
  * shape reached (the geometry picks one of several hundred from the mode, the op, the window, the
  * client count, the device's CU count and fa_set_reduce_grid).  The launch path only stores a
@@ -400,6 +400,30 @@ int64_t fa_gram_workspace(int32_t n_clients, int64_t n_cols);
 int fa_gram_f32(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
                 int64_t col_begin, int64_t n_cols, void* workspace, int64_t workspace_bytes,
                 double* gram_out, void* stream);
+
+/* fa_gram_f32 for up to FA_GRAM_WIDE_MAX_CLIENTS clients: the same matrix, arguments, errors and
+ * order of checks, with this cap in place of FA_GRAM_MAX_CLIENTS.  Opt-in:
+ * fa_gram_f32 and fa_gram_workspace keep refusing client 129.  With n_clients <= FA_GRAM_MAX_CLIENTS
+ * both entries are fa_gram_workspace's answer and fa_gram_f32's launch, bit for bit and in
+ * fa_last_launch.  With 129 <= n_clients <= 1024 the rows are grouped into panels of 128 and the
+ * window into column slices; one block multiplies one pair of panels (I <= J) over one slice on the
+ * matrix cores, under fa_gram_f32's arithmetic contract (exact fp32 products, a k-ordered fp32 chain
+ * of at most 1024 columns folded into an outer fp32 tile), and stores a 128 x 128 fp32 partial to
+ * `workspace`; a second kernel sums the slices of each entry in float64 in slice order.  The same
+ * inputs on the same device and grid give the same bits, gram_out is symmetric bit for bit, a
+ * non-finite value in row i touches row i and column i only, and
+ * |error| <= (gamma(chain) + slices * 2^-52) * sum_k |y_i[k] y_j[k]| with chain and slices from
+ * plan_gram_wide (csrc/fa_gramwide_geometry.hpp).  fa_gram_wide_workspace: at most 2048 partial
+ * tiles (128 MiB), enough on any device and under any fa_set_reduce_grid, never smaller for more
+ * clients or columns; HOST function, no HIP call.  Every error is decided before any HIP call.
+ * fa_set_reduce_grid forces the number of column slices (capped at 2048 / pairs and at the window's
+ * 64-column chunks); fa_last_launch names the pair kernel and its grid, slices * pairs, e.g.
+ * "panel_pair_kernel<true>", launches = 2.  ABI 30.                                               */
+#define FA_GRAM_WIDE_MAX_CLIENTS 1024
+int64_t fa_gram_wide_workspace(int32_t n_clients, int64_t n_cols);
+int fa_gram_f32_wide(const float* stack, int64_t row_stride, int32_t n_clients, const float* center,
+                     int64_t col_begin, int64_t n_cols, void* workspace, int64_t workspace_bytes,
+                     double* gram_out, void* stream);
 
 /* ---- robust aggregation: norm-clipped rounds -----------------------------
  * Every client's update x_i - g is projected onto a ball of radius tau around the server's model g
